@@ -1,7 +1,15 @@
 """Benchmark: batch secp256k1 ECDSA verify on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run does what the headline figure needs and no more: it generates the
+batch, warms up, times the K steps, checks the verdict bitmap against the
+construction labels, writes the last step's verdicts when --dump-outputs DIR
+is given (DIR/verdicts.npy, see dump_outputs) and prints the result line.
+--full adds every other leg described below (the CPU checker and baseline,
+configs[0] / [2] / [3], headers, merkle roots, the host and in-process paths);
+without it their fields in the line are null.
 
 Without a launcher (WORLD_SIZE unset), --gpus N > 1 starts N rank processes
 itself (fresh interpreters with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; the
@@ -30,7 +38,11 @@ max-over-ranks time. After the timed steps every rank checks its slice of
 the gathered bitmap against its labels and the counts are summed
 (`mismatches`: every bit of the global bitmap against its record's label).
 
-Also reported (rank 0, N = 1): the ecmult stage's roofline (the REFERENCE
+With --full every rank also re-verifies its slice on the host
+(`mismatches_vs_checker`).
+
+Also reported (rank 0, N = 1; configs[0] onwards with --full only): the
+ecmult stage's roofline (the REFERENCE
 algorithm's limb products per verify, hkv/opcount.py P_ALG_ECMULT, over the
 HIP-event-timed ecmult + finish launches, against the v_mad_u64_u32 peak at 2.4 GHz and at the
 measured mad rate and clock); configs[0] (the 2,000-tx P2PKH block), [2]
@@ -69,6 +81,27 @@ CONFIG4_INVALID_PERMILLE = 50
 # computes it, with and without the RCCL all-gather (profiles/r06a/, r06f/):
 # SURVEY §8(e)'s check that the N-GPU bitmap is bit-identical to the 1-GPU one
 CONFIG4_BITMAP_SHA = "3d2b3fc0ad2eacaae04c9f12bc5c16e0"
+# --dump-outputs: at most this many verdicts are written (float32: 16 MiB);
+# of a larger batch a fixed sample, drawn with this seed
+DUMP_MAX = 1 << 22
+DUMP_SEED = 0x484B5644
+
+
+def dump_outputs(path: str, bitmap, n: int) -> None:
+    """--dump-outputs DIR: what the timed path returned in its last step, the
+    global verdict bitmap (uint32 words, bit k % 32 of word k // 32 = record
+    k), as DIR/verdicts.npy: float32 [n], 1.0 = accepted, record order. Of a
+    batch over DUMP_MAX records, the verdicts of DUMP_MAX records drawn
+    without replacement by default_rng(DUMP_SEED), in ascending record order:
+    the same records in every run with the same n. The batch is generated
+    from its seed, so two builds run with the same arguments write verdicts
+    of identical inputs."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    bits = np.unpackbits(np.ascontiguousarray(bitmap).view(np.uint8), bitorder="little")[:n]
+    if n > DUMP_MAX:
+        bits = bits[np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX, replace=False))]
+    np.save(os.path.join(path, "verdicts.npy"), bits.astype(np.float32))
 
 
 def cgroup_cpu_quota() -> dict:
@@ -986,6 +1019,8 @@ def mock_main(args, world: int, rank: int) -> None:
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     full = sv.bitmap()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full, n_total)
     lab = bits_from_bools(mock_pattern(np.arange(sv.lo, sv.hi)).astype(bool))
     chk = torch.tensor([sv.slice_mismatches(full, lab)], dtype=torch.int64)
     devs = [{"rank": rank, "device": "cpu", "pid": os.getpid()}]
@@ -1014,6 +1049,13 @@ def main() -> None:
     ap.add_argument("--mock-cpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's verdicts to DIR/verdicts.npy (float32, one per "
+                         "record; a fixed seeded sample of a batch over 4,194,304 records)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the CPU checker over the slice, and at N = 1 "
+                         "configs[0] / [2] / [3], headers, merkle roots, the host and in-process paths and the CPU "
+                         "baseline (each still switched off by its --no-* option)")
     ap.add_argument("--per-gpu", type=int, default=PER_GPU)
     ap.add_argument("--mode", type=int, default=0, help="0 = HKV_LIBSECP, 1 = HKV_HASKOIN")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1156,6 +1198,8 @@ def main() -> None:
     # summed over the ranks (outside the timed region), so every bit of the
     # gathered bitmap is checked against the label of the same global record
     full = sv.bitmap()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full, n_total)
     lab_np = labels.cpu().numpy().view(np.uint32)
     # and the gathered bitmap's slice against the rank's own words as the
     # verify wrote them (before the collective): a gather that lost, moved
@@ -1169,9 +1213,10 @@ def main() -> None:
     if use_dist:
         dist.all_reduce(chk, op=dist.ReduceOp.SUM)
     mismatches, accepted, label_valid, gather_vs_local = chk.tolist()
-    # the same slice against the CPU checker, every record (summed over ranks)
+    # the same slice against the CPU checker, every record (summed over ranks;
+    # --full only)
     chkr = None
-    if not args.no_checker:
+    if args.full and not args.no_checker:
         mine = np.unpackbits(full.view(np.uint8), bitorder="little")[sv.lo:sv.hi].astype(bool)
         chkr = checker_leg(recs.cpu().numpy(), mine, args.mode)
         ct = torch.tensor([chkr["checked"], -1 if chkr["mismatches"] is None else chkr["mismatches"],
@@ -1208,7 +1253,7 @@ def main() -> None:
         traffic, traffic_raw = load_traffic(args.traffic_json, n)
         c0 = mix = hp = hdr = mkl = adv = None
         c0_recs = c0_got = c0_txs = c0_inputs = adv_recs = adv_got = None
-        single = world == 1 and not config4  # the N = 1 headline run carries the other legs
+        single = args.full and world == 1 and not config4  # --full: the N = 1 headline run carries the other legs
         if single and not args.no_config0:
             c0, c0_recs, c0_got, c0_txs, c0_inputs = config0_block(v, torch, args.steps)
             c0["records_vs_oracle"] = config0_records_check(c0_txs, c0_inputs, c0_recs)
@@ -1274,6 +1319,7 @@ def main() -> None:
                          "external" if world > 1 else "single process"),
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(dt_max / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if config4 else "weak",

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export PYTHONUNBUFFERED=1
 TAG=${TAG:-ablib}
-B="bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-adversarial --no-headers --no-merkle --no-host-path"
+B="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-adversarial --no-headers --no-merkle --no-host-path"
 timeout -k 10 ${PYTEST_LIMIT:-900} python -u -m pytest tests -x -v -m gpu --timeout 800 --timeout-method thread > gpurun_out/${TAG}_pytest.log 2>&1 \
   && echo "pytest ok" && tail -1 gpurun_out/${TAG}_pytest.log || exit 1
 for k in 1 2; do

@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 TAG=${TAG:-abvar}
-B="bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-adversarial --no-headers --no-merkle --no-host-path --no-inproc --no-checker"
+B="bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-adversarial --no-headers --no-merkle --no-host-path --no-inproc --no-checker"
 for k in 1 2; do
   for v in base ${VARIANTS}; do
     if [ $v = base ]; then unset HKV_LIB; else export HKV_LIB=haskoin-node_amd/lib/libhkv_$v.so; fi

@@ -35,7 +35,7 @@ export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 MODE=${1:?mode: evidence | suite | benches | node | stress}
 TAG=${2:-$MODE}
 O=gpurun_out/${TAG}
-S="--no-cpu-baseline --no-block-mix --no-config0 --no-adversarial --no-headers --no-merkle --no-host-path --no-inproc"
+S="--full --no-cpu-baseline --no-block-mix --no-config0 --no-adversarial --no-headers --no-merkle --no-host-path --no-inproc"
 
 summary() {  # bench JSON lines -> one line each
   for f in "$@"; do
@@ -60,14 +60,14 @@ suite_half() {
 }
 
 benches_half() {
-  timeout -k 10 600 python bench.py > ${O}_bench1.log 2>&1 && echo "bench1 ok" \
-    && timeout -k 10 600 python bench.py > ${O}_bench2.log 2>&1 && echo "bench2 ok" \
-    && timeout -k 10 300 python bench.py --gpus 2 --share-device --config4-n 2097152 --steps 5 --warmup 1 \
+  timeout -k 10 600 python bench.py --full > ${O}_bench1.log 2>&1 && echo "bench1 ok" \
+    && timeout -k 10 600 python bench.py --full > ${O}_bench2.log 2>&1 && echo "bench2 ok" \
+    && timeout -k 10 300 python bench.py --full --gpus 2 --share-device --config4-n 2097152 --steps 5 --warmup 1 \
          > ${O}_spawn2.log 2>&1 && echo "spawn2 ok" \
-    && timeout -k 10 300 python bench.py --gpus 1 --force-collective --config4 --steps 5 --warmup 1 \
+    && timeout -k 10 300 python bench.py --full --gpus 1 --force-collective --config4 --steps 5 --warmup 1 \
          > ${O}_rccl1.log 2>&1 && echo "rccl1 ok" \
     && timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-         --master-port 29533 bench.py --gpus 1 --force-collective --config4 --steps 5 --warmup 1 \
+         --master-port 29533 bench.py --full --gpus 1 --force-collective --config4 --steps 5 --warmup 1 \
          > ${O}_torchrun_rccl1.log 2>&1 && echo "torchrun rccl1 ok" \
     && { timeout -k 10 120 python bench.py --gpus 2 --steps 2 > ${O}_gpus2.log 2>&1; rc=$?;
          echo "--gpus 2 on the 1-GPU lease: rc=$rc (want 2)"; [ $rc -eq 2 ]; } \
@@ -97,7 +97,7 @@ node)
     && timeout -k 10 300 python bench.py --config4 --config4-n 2097152 --steps 10 --warmup 2 $S > ${O}_c4_2M.log 2>&1 \
     && timeout -k 10 300 python bench.py --config4 --config4-n 8388608 --steps 5 --warmup 1 $S > ${O}_c4_8M.log 2>&1 \
     && timeout -k 10 300 python bench.py --steps 10 --warmup 2 $S > ${O}_c1.log 2>&1 \
-    && timeout -k 10 400 python bench.py --steps 8 --warmup 1 --std-ibd 560000 --no-cpu-baseline --no-config0 \
+    && timeout -k 10 400 python bench.py --full --steps 8 --warmup 1 --std-ibd 560000 --no-cpu-baseline --no-config0 \
          --no-adversarial --no-headers --no-merkle --no-host-path --no-inproc --no-checker > ${O}_ibd.log 2>&1 \
     && summary ${O}_c4_2M.log ${O}_c4_8M.log ${O}_c1.log \
     && timeout -k 10 200 python3 tools/soak.py 120 15 > ${O}_soak.json 2> ${O}_soak.err \

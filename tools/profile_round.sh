@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 # verify only, so the ecmult counters are those of the timed launch
 # (--no-host-path / --no-inproc: their hkv_verify chunks run the same 262,144-lane
 # ecmult grid over more records per launch and would mix into its statistics)
-FULL="bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-host-path --no-inproc ${BENCH_ARGS}"
+FULL="bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-host-path --no-inproc ${BENCH_ARGS}"
 BENCH="bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-block-mix --no-config0 --no-adversarial --no-headers --no-merkle --no-host-path --no-inproc ${BENCH_ARGS}"
 run() {  # name, rocprof args...
   local name=$1; shift
