@@ -21,6 +21,7 @@
 #include "hkv_internal.h"
 #include "hkv_layout.h"
 #include "hkv_plan.h"
+#include "hkv_tail_plan.h"
 
 #ifndef HKV_BLOCK_ROWS  // the block kernel builds its inputs' tx index rows (0: an index launch first)
 #define HKV_BLOCK_ROWS 1
@@ -165,13 +166,9 @@ size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 #ifndef HKV_STD_CHUNK
 #define HKV_STD_CHUNK (1u << 20)
 #endif
-constexpr size_t MS_CAND_PER_INPUT = 136, MS_KEYS_PER_INPUT = 16;
-#ifndef HKV_MS_WIN_CAND
-#define HKV_MS_WIN_CAND 2752512u  // 43,008 x 64 candidate records (441 MiB)
-#endif
-#ifndef HKV_MS_WIN_KEYS
-#define HKV_MS_WIN_KEYS 442368u   // 6,912 x 64 key-check records (71 MiB)
-#endif
+// (hkv_tail_plan.h: the bound and the verdict-word sizes the tail's plan is checked against)
+constexpr size_t MS_CAND_PER_INPUT = hkv::MS_CAND_PER_INPUT, MS_KEYS_PER_INPUT = hkv::MS_KEYS_PER_INPUT;
+// (HKV_MS_WIN_CAND / HKV_MS_WIN_KEYS, the windows' budget: hkv_tail_plan.h)
 constexpr size_t HKV_MAX_STD_INPUTS = 0xFFFFFF00ull;
 constexpr size_t MS_BAR_WORDS = 32, MS_FAULT = 16, MS_HOST_STATUS = 17;  // DevCtx::ms_bar
 #ifndef HKV_HOST_FIRST_DIV  // the host-batch path's first chunk: one resident grid / this
@@ -577,14 +574,14 @@ int enqueue_std_chunk(DevCtx& d, const hkv_txs* dt, const hkv_input_job* jobs, s
   // else the budget (hkv_debug_ms_window can shrink both for tests)
   const size_t win_c = d.ms_win_cand ? d.ms_win_cand : HKV_MS_WIN_CAND;
   const size_t win_k = d.ms_win_keys ? d.ms_win_keys : HKV_MS_WIN_KEYS;
-  const size_t cap_cand = round_up(std::min(all_cand, win_c), 64), cap_keys = round_up(std::min(all_keys, win_k), 64);
+  const size_t cap_cand = hkv::ms_window_records(all_cand, win_c), cap_keys = hkv::ms_window_records(all_keys, win_k);
   const size_t slots = hkv::ms_tail_slots((uint32_t)d.n_cu);
   int rc = grow(&d.ms[0], &d.ms_cap[0], n * 8, "hipMalloc(multisig desc)");
   if (!rc) rc = grow(&d.ms[2], &d.ms_cap[2], n * 8, "hipMalloc(multisig offsets)");
-  if (!rc) rc = grow(&d.ms[3], &d.ms_cap[3], round_up(all_cand, 64) / 8, "hipMalloc(multisig candidate bits)");
+  if (!rc) rc = grow(&d.ms[3], &d.ms_cap[3], hkv::ms_cbits_words(n) * 4, "hipMalloc(multisig candidate bits)");
   // (the key window starts right after this call's candidate window)
   if (!rc) rc = grow(&d.ms[4], &d.ms_cap[4], (cap_cand + cap_keys) * hkv::REC_SIZE, "hipMalloc(multisig records)");
-  if (!rc) rc = grow(&d.ms[5], &d.ms_cap[5], round_up(all_keys, 64) / 8, "hipMalloc(multisig key bits)");
+  if (!rc) rc = grow(&d.ms[5], &d.ms_cap[5], hkv::ms_kbits_words(n) * 4, "hipMalloc(multisig key bits)");
   // the tail's candidate groups use slot-relative pair-form scratch (grid * 32 signatures)
   if (!rc) rc = ensure_dev_buffers(d, std::max(round_up(n, hkv::WG), round_up(slots, hkv::WG)));
   if (!rc) rc = ensure_aux(d, std::max(round_up(n, hkv::WG), round_up(slots, hkv::WG)), st);
@@ -834,6 +831,32 @@ int hkv_debug_ms_scratch(hkv_ctx* ctx, int dev, size_t* bytes) {
   std::lock_guard<std::mutex> lock(ctx->mu);
   *bytes = ctx->devs[(size_t)dev].ms_cap[4];
   return HKV_OK;
+}
+
+int hkv_debug_ms_tail_counts(hkv_ctx* ctx, int dev, uint64_t out[3]) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size() || !out) return HKV_E_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DevCtx& d = ctx->devs[(size_t)dev];
+  out[0] = out[1] = out[2] = 0;
+  if (d.tail_epoch == 0 || !d.ms_ctr || !d.ms_bar) return HKV_OK;  // no tail launched yet
+  HKV_TRY(hipSetDevice(d.device), "hipSetDevice");
+  // after every call enqueued so far on this device (the scratch order): the
+  // last launch's scan sum and queue slot stay as it left them until the
+  // next launch zeroes them when it starts (read only)
+  const uint32_t par = (d.tail_epoch - 1u) & 1u;
+  uint64_t total = 0;
+  unsigned int slot[2] = {0, 0};  // claim, done (hkv_kernels.hip TQ_CLAIM, TQ_DONE; slots of 8 words)
+  int rc = scratch_acquire(d, d.stream);
+  if (rc) return rc;
+  HKV_TRY(hipMemcpyAsync(&total, static_cast<uint64_t*>(d.ms_ctr) + par, sizeof(total), hipMemcpyDeviceToHost,
+                         d.stream),
+          "D2H scan total");
+  HKV_TRY(hipMemcpyAsync(slot, d.ms_bar + par * 8u, sizeof(slot), hipMemcpyDeviceToHost, d.stream), "D2H tail slot");
+  HKV_TRY(hipStreamSynchronize(d.stream), "tail counts sync");
+  out[0] = total;
+  out[1] = slot[0];
+  out[2] = slot[1];
+  return scratch_release(d, d.stream);
 }
 
 int hkv_device_fault(hkv_ctx* ctx, int dev, uint32_t* fault) {

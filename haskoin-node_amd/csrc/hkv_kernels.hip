@@ -34,6 +34,7 @@
 #include "hkv_layout.h"
 #include "hkv_internal.h"
 #include "hkv_sighash_dev.h"
+#include "hkv_tail_plan.h"
 
 namespace hkv {
 
@@ -2604,7 +2605,11 @@ namespace hkv {
 //     [r * win, (r + 1) * win) of the scan's allocation: the emit writes
 //     only the records in the round's windows (hashing only the signatures
 //     with one there), the verifies read them and write their verdict bits
-//     at the global index. Phase 4 reads every round's bits.
+//     at the global index. Phase 4 reads every round's bits. A round has
+//     items only for the records it holds (none for an empty window; the
+//     last group's valid slots end at the round's end): the queue's
+//     arithmetic is hkv_tail_plan.h, walked item by item on the CPU against
+//     a model of these buffers by tests/tail_plan.cpp.
 // ---------------------------------------------------------------------------
 // ---------------------------------------------------------------------------
 enum : uint32_t { TQ_CLAIM = 0, TQ_DONE = 1, TQ_SLOT = 8 };  // slot words: claim, done (completed items)
@@ -2639,7 +2644,8 @@ __global__ void __launch_bounds__(PAIR_TPB, 1) hkv_ms_tail_kernel(MsTail a) {
   __shared__ HLane hlds[2];
   __shared__ uint32_t xch[25 * PAIR_SIGS];
   __shared__ uint32_t buf[16 * PAIR_TPB];  // sha256_stream blocks ([word][thread])
-  __shared__ uint32_t item_s, go_s;
+  __shared__ TailItem item_s;  // the claimed item (thread 0's tail_item)
+  __shared__ uint32_t go_s;
   // this launch's queue slot and scan sum (zeroed by the launch before this
   // one on the device's ordered stream of calls); workgroup 0 zeroes the
   // other slot and sum, the next launch's
@@ -2655,94 +2661,82 @@ __global__ void __launch_bounds__(PAIR_TPB, 1) hkv_ms_tail_kernel(MsTail a) {
   const uint32_t n_cand = (uint32_t)total, n_keys = (uint32_t)(total >> 32);
   if (n_keys == 0) return;  // no multisig input (every input has >= 1 key): uniform over the grid
   const uint32_t T = PAIR_TPB;
-  const uint32_t Wc = a.win_cand, Wk = a.win_keys;  // (multiples of 64, >= 64)
-  const uint32_t rounds = max((n_cand + Wc - 1) / Wc, (n_keys + Wk - 1) / Wk);
-  const uint32_t wc = min(Wc, n_cand), wk = min(Wk, n_keys);  // records per (full) round
+  // the queue's items, rounds and ranges: hkv_tail_plan.h, and nothing here
+  // (windows: multiples of 64, >= 64)
   const uint32_t n1 = (a.hash_txs != TX_HASHES_NONE) ? (3 * a.n_tx + T - 1) / T : 0;  // hash chunks
-  const uint32_t n2 = (a.n + T - 1) / T;                                                // record chunks
-  const uint32_t n3k = (wk + T - 1) / T, n3 = n3k + (wc + PAIR_SIGS - 1) / PAIR_SIGS;  // per round
-  const uint32_t per = n2 + n3;
-  const uint32_t e1 = n1, e3 = e1 + rounds * per, e4 = e3 + n2;
+  const TailPlan plan = tail_plan(a.n, n1, n_cand, n_keys, a.win_cand, a.win_keys, T, PAIR_SIGS);
   const uint32_t slots = gridDim.x * PAIR_SIGS, sbase = blockIdx.x * PAIR_SIGS;
   const StdArgs none{};
   uint32_t seen = 0;  // the first item index of the latest phase known complete before it (this workgroup's view)
   for (;;) {
     if (threadIdx.x == 0) {
       const uint32_t it = atomicAdd(&q[TQ_CLAIM], 1u);
-      uint32_t ok = it < e4 ? 1u : 0u;
-      // the first item of this item's phase: every item before it must have
-      // completed (items are claimed in phase order, so only running items
-      // can be outstanding)
-      uint32_t start = 0;
-      if (it >= e3) start = e3;
-      else if (it >= e1) {
-        const uint32_t r0 = e1 + (it - e1) / per * per;
-        start = it - r0 < n2 ? r0 : r0 + n2;
+      uint32_t ok = it < plan.e4 ? 1u : 0u;
+      // x.start, the first item of this item's phase: every item before it
+      // must have completed (items are claimed in phase order, so only
+      // running items can be outstanding)
+      if (ok) {
+        const TailItem x = tail_item(plan, it);
+        if (x.start > seen) {
+          ok = tail_wait(a, &q[TQ_DONE], x.start) ? 1u : 0u;
+          if (ok) seen = x.start;
+        }
+        item_s = x;
       }
-      if (ok && start > seen) {
-        ok = tail_wait(a, &q[TQ_DONE], start) ? 1u : 0u;
-        if (ok) seen = start;
-      }
-      item_s = it;
       go_s = ok;
     }
     __syncthreads();
-    const uint32_t it = item_s, go = go_s;
+    const TailItem x = item_s;
+    const uint32_t go = go_s;
     __syncthreads();
     if (!go) return;
-    if (it < e1) {
+    if (x.kind == TAIL_HASH) {
       // 1. the BIP143 per-tx hashes (lanes hash-major, so a wave mostly
       //    shares its hash). Every tx of the batch is hashed, and the block
       //    kernel built index rows only for the txs its inputs reference (a
       //    block's coinbase has none), so each lane re-derives its tx's row
       //    from the offsets — a stale row of an earlier call would point the
       //    hash outside the tx — and writes back only the hash words.
-      const uint32_t x = it * T + threadIdx.x;
-      bool go1 = x < 3 * a.n_tx;
-      const uint32_t t = go1 ? x % a.n_tx : 0, which = go1 ? x / a.n_tx : 0;
+      const uint32_t t_ = x.idx * T + threadIdx.x;
+      bool go1 = t_ < 3 * a.n_tx;
+      const uint32_t t = go1 ? t_ % a.n_tx : 0, which = go1 ? t_ / a.n_tx : 0;
       uint32_t row[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       if (go1) tx_index_row(a.txs, a.tx_off, t, row);
       if (go1 && a.hash_txs == TX_HASHES_WITNESS) go1 = (row[TXT_FLAGS] & TXF_WITNESS) != 0;
       tx_hash_word_lane(a.txs, row, a.txt + (size_t)t * TXT_WORDS, which, go1, buf);
-    } else if (it < e3) {
-      const uint32_t r = (it - e1) / per, k0 = (it - e1) % per;
-      const uint32_t cw0 = r * Wc, kw0 = r * Wk;  // the round's windows (global record indices)
-      if (k0 < n2) {
-        // 2. key-check and candidate records of the round's windows
-        const uint32_t jx = k0 * T + threadIdx.x;
-        ms_emit_lane(a.txs, a.n_tx, a.txt, a.scripts, a.scripts_len, a.jobs, jx, jx < a.n, a.forkid, a.desc, a.off,
-                     a.cand, a.keyrec, cw0, Wc, kw0, Wk, buf);
-      } else if (k0 - n2 < n3k) {
-        // 3a. a chunk of the round's key checks (bits at the global index)
-        const uint32_t i = kw0 + (k0 - n2) * T + threadIdx.x;
-        key_check_lane(reinterpret_cast<const uint32_t*>(a.keyrec), i, min(n_keys, kw0 + Wk), a.kbits, kw0);
-      } else {
-        // 3b. a pair-form group of 32 of the round's candidates on this
-        //     workgroup's own scratch slots [sbase, sbase + 32): pair_group
-        //     indexes records and verdict words by slot, so both are handed
-        //     over shifted — the verdict words by base - sbase (base = the
-        //     group's global index), the records by base - cw0 - sbase (their
-        //     place in the window) — which is negative when the group lies
-        //     below the slot (a queue hands any group to any workgroup):
-        //     formed on the 64-bit address as an integer, never as an
-        //     out-of-range pointer, and every access lands at a record and a
-        //     verdict word of the group
-        const uint32_t base = cw0 + (k0 - n2 - n3k) * PAIR_SIGS;
-        const int64_t shift = (int64_t)base - (int64_t)sbase;  // a multiple of 32
-        const int64_t rshift = shift - (int64_t)cw0;
-        uint32_t* recs = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(a.cand) +
-                                                     (uintptr_t)(rshift * (int64_t)(REC_WORDS * 4)));
-        uint32_t* bits = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(a.cbits) +
-                                                     (uintptr_t)(shift / 32 * 4));
-        // slot i is record i + shift: valid iff i + shift < the round's end
-        // (mod 2^32: end - shift < 2^32)
-        const uint32_t end = min(n_cand, cw0 + Wc);
-        pair_group<false>(sbase, a.im, (uint32_t)((int64_t)end - shift), slots, a.gtab, bits, 0xFFFFFFFFu, a.aux,
-                          recs, HKV_MODE_HASKOIN, nullptr, none, qlds, hlds, xch, buf);
-      }
+    } else if (x.kind == TAIL_EMIT) {
+      // 2. key-check and candidate records of the round's windows (global
+      //    record indices from x.cw0 / x.kw0)
+      const uint32_t jx = x.idx * T + threadIdx.x;
+      ms_emit_lane(a.txs, a.n_tx, a.txt, a.scripts, a.scripts_len, a.jobs, jx, jx < a.n, a.forkid, a.desc, a.off,
+                   a.cand, a.keyrec, x.cw0, plan.Wc, x.kw0, plan.Wk, buf);
+    } else if (x.kind == TAIL_KEYS) {
+      // 3a. a chunk of the round's key checks (bits at the global index)
+      key_check_lane(reinterpret_cast<const uint32_t*>(a.keyrec), x.first + threadIdx.x, x.end, a.kbits, x.kw0);
+    } else if (x.kind == TAIL_CAND) {
+      // 3b. a pair-form group of 32 of the round's candidates on this
+      //     workgroup's own scratch slots [sbase, sbase + 32): pair_group
+      //     indexes records and verdict words by slot, so both are handed
+      //     over shifted — the verdict words by base - sbase (base = the
+      //     group's global index), the records by base - cw0 - sbase (their
+      //     place in the window) — which is negative when the group lies
+      //     below the slot (a queue hands any group to any workgroup):
+      //     formed on the 64-bit address as an integer, never as an
+      //     out-of-range pointer, and every access lands at a record and a
+      //     verdict word of the group
+      const int64_t shift = (int64_t)x.base - (int64_t)sbase;  // a multiple of 32
+      const int64_t rshift = shift - (int64_t)x.cw0;
+      uint32_t* recs = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(a.cand) +
+                                                   (uintptr_t)(rshift * (int64_t)(REC_WORDS * 4)));
+      uint32_t* bits = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(a.cbits) +
+                                                   (uintptr_t)(shift / 32 * 4));
+      // slot sbase + i is record base + i: valid iff i < x.valid (1..32: the
+      // plan has no group past the round's end)
+      pair_group<false>(sbase, a.im, sbase + x.valid, slots, a.gtab, bits, 0xFFFFFFFFu, a.aux, recs,
+                        HKV_MODE_HASKOIN, nullptr, none, qlds, hlds, xch, buf);
     } else {
       // 4. the countMulSig walk
-      const uint32_t jx = (it - e3) * T + threadIdx.x;
+      const uint32_t jx = x.idx * T + threadIdx.x;
       ms_resolve_lane(a.desc, a.off, jx, jx < a.n, a.cbits, a.kbits, a.out_bits);
     }
     publish_count(&q[TQ_DONE]);

@@ -39,7 +39,11 @@ def varint(n: int) -> bytes:
 
 
 def push(data: bytes) -> bytes:
-    return bytes([len(data)]) + data if len(data) <= 75 else b"\x4c" + bytes([len(data)]) + data
+    if len(data) <= 75:
+        return bytes([len(data)]) + data
+    if len(data) <= 255:
+        return b"\x4c" + bytes([len(data)]) + data
+    return b"\x4d" + struct.pack("<H", len(data)) + data  # OP_PUSHDATA2 (a redeem script of 8 or more keys)
 
 
 def der(r: bytes, s: bytes) -> bytes:
@@ -216,7 +220,8 @@ def multisig_script(m: int, pubs: List[bytes]) -> bytes:
 
 def make_multisig_block(verifier, torch, n_tx: int, seed: int = MULTISIG_SEED, n_keys: int = 4096,
                         shapes=((1, 1), (1, 2), (2, 2), (2, 3), (1, 3), (3, 3)),
-                        wraps=("p2sh", "bare", "p2wsh", "p2sh_p2wsh"), invalid_permille: int = 80
+                        wraps=("p2sh", "bare", "p2wsh", "p2sh_p2wsh"), invalid_permille: int = 80,
+                        damage_kinds=("wrong_key", "swap", "drop")
                         ) -> Tuple[List[bytes], List[Tuple[int, int, bytes, int]]]:
     """n_tx txs of one CHECKMULTISIG input each (m-of-n over compressed keys
     from a device-generated pool, bare or behind P2SH / P2WSH / P2SH-P2WSH,
@@ -225,7 +230,10 @@ def make_multisig_block(verifier, torch, n_tx: int, seed: int = MULTISIG_SEED, n
     witness script otherwise) comes from hkv_sighash, the signatures from
     hkv_gen_sign_device. About invalid_permille / 1000 of the inputs are
     damaged — a signer's signature made with another key, or two signatures
-    swapped (m >= 2), or one signature dropped — so some verdicts reject.
+    swapped (m >= 2), or one signature dropped (damage_kinds: the kinds drawn
+    from; "wrong_key" and "swap" keep every signature in place and decodable,
+    so the input's candidate count stays that of its shape) — so some
+    verdicts reject.
     Returns (txs, inputs) as make_block does; the verdicts are the oracle's
     to decide (tests/test_gpu_ms_window.py)."""
     import hashlib
@@ -249,7 +257,7 @@ def make_multisig_block(verifier, torch, n_tx: int, seed: int = MULTISIG_SEED, n
         value = rng.randrange(1000, 2**45)
         signers = sorted(rng.sample(range(n), m))
         damage = rng.randrange(1000) < invalid_permille
-        kind = rng.choice(["wrong_key", "swap", "drop"]) if damage else None
+        kind = rng.choice(list(damage_kinds)) if damage else None
         if kind == "swap" and m < 2:
             kind = "wrong_key"
         sign_keys = [kidx[j] for j in signers]

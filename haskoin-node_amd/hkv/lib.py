@@ -73,6 +73,7 @@ EXPORTS = {
     "hkv_debug_fail_device": (c_int, [c_void_p, c_int, c_uint32]),
     "hkv_debug_ms_window": (c_int, [c_void_p, c_int, c_uint32, c_uint32]),
     "hkv_debug_ms_scratch": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "hkv_debug_ms_tail_counts": (c_int, [c_void_p, c_int, POINTER(c_uint64)]),
     "hkv_batch_alloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "hkv_batch_free": (None, [c_void_p]),
     "hkv_batch_records": (POINTER(c_uint8), [c_void_p]),

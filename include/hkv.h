@@ -130,6 +130,13 @@ int hkv_debug_fail_device(hkv_ctx* ctx, int dev, uint32_t when);
  * _scratch reports the bytes the windows hold allocated on device dev. */
 int hkv_debug_ms_window(hkv_ctx* ctx, int dev, uint32_t cand_records, uint32_t key_records);
 int hkv_debug_ms_scratch(hkv_ctx* ctx, int dev, size_t* bytes);
+/* Read-only test hook: what device dev's last multisig tail launch saw and
+ * did, read after every call enqueued so far has completed. out[0] = the
+ * scan's total it ran on (candidate records | key-check records << 32),
+ * out[1] = work-queue items claimed (each workgroup's final claim past the
+ * last item included), out[2] = items completed. All 0 before the first
+ * call. Changes no state. */
+int hkv_debug_ms_tail_counts(hkv_ctx* ctx, int dev, uint64_t out[3]);
 
 /* Pinned host record buffer with room for max_n records. */
 int hkv_batch_alloc(hkv_ctx* ctx, size_t max_n, hkv_batch** out);
