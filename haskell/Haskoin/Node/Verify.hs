@@ -35,6 +35,9 @@ module Haskoin.Node.Verify
     verifyRawBatch,
     verifyHashSigBatch,
     verifyStdInputBatch,
+    txHashBatch,
+    BlockCheck (..),
+    checkBlocksBatch,
     VerifyConfig (..),
     VerifyEvent (..),
     VerifyActor,
@@ -58,9 +61,9 @@ import Data.Word (Word32, Word64, Word8)
 import Foreign.C.String (peekCString)
 import GHC.Clock (getMonotonicTimeNSec)
 import Foreign.Marshal.Alloc (alloca)
-import Foreign.Marshal.Array (allocaArray, withArray)
+import Foreign.Marshal.Array (allocaArray, peekArray, withArray)
 import Foreign.Marshal.Utils (copyBytes, fillBytes, with)
-import Foreign.Ptr (Ptr, castPtr, plusPtr)
+import Foreign.Ptr (Ptr, castPtr, nullPtr, plusPtr)
 import Foreign.Storable (peek, peekElemOff, pokeByteOff)
 import Haskoin
   ( Block (..),
@@ -223,6 +226,70 @@ verifyStdInputBatch v net txs ins = withMVar v.lock $ \_ -> do
               c_hkv_verify_std_inputs v.ctx ptxs pjobs (fromIntegral n) forkid bits
                 >>= check "hkv_verify_std_inputs" . fromIntegral
               readBits n bits
+
+-- | The serialised txs of a batch as an @hkv_txs@ without a script pool:
+-- each tx's @runPutS . serialize@ back to back, offsets as prefix sums.
+withRawTxs :: [ByteString] -> (Ptr HkvTxs -> IO a) -> IO a
+withRawTxs raws f =
+  BU.unsafeUseAsCString (B.concat raws) $ \pbytes ->
+    withArray (scanl (+) 0 (map (fromIntegral . B.length) raws) :: [Word32]) $ \poffs ->
+      with (HkvTxs (castPtr pbytes) poffs (fromIntegral (length raws)) nullPtr 0) f
+
+-- | Element i equals @runPutS (serialize (txHash tx_i))@ (haskoin-core): the
+-- 32 digest-order bytes of SHA-256d over the tx re-serialised without witness
+-- data, computed on the GPU from the wire form. A tx haskoin serialised always
+-- parses; should the library still report HKV_TXID_BAD_TX that is an error.
+txHashBatch :: Verifier -> [Tx] -> IO [ByteString]
+txHashBatch _ [] = return []
+txHashBatch v txs = withMVar v.lock $ \_ ->
+  withRawTxs (map (runPutS . serialize) txs) $ \ptxs ->
+    allocaArray (32 * n) $ \out ->
+      allocaArray n $ \st -> do
+        c_hkv_tx_ids v.ctx ptxs out st >>= check "hkv_tx_ids" . fromIntegral
+        bad <- any (== hkvTxidBadTx) <$> peekArray n st
+        when bad $ throwIO (VerifierException "hkv_tx_ids: a serialised tx did not parse" (-1))
+        mapM (\i -> B.packCStringLen (castPtr out `plusPtr` (32 * i), 32)) [0 .. n - 1]
+  where
+    n = length txs
+
+-- | What the GPU found for one block.
+data BlockCheck = BlockCheck
+  { -- | @b.header.merkle == buildMerkleRoot (txHash <$> b.txs)@, the
+    -- reference's assertion on getBlocks results (NodeSpec.hs:185-193)
+    merkleOk :: !Bool,
+    -- | two equal hashes were paired at some level (CVE-2012-2459)
+    mutated :: !Bool,
+    -- | the block has no transaction (merkleOk is False)
+    empty :: !Bool,
+    -- | the computed root, digest order
+    root :: !ByteString
+  }
+
+-- | One GPU call for a batch of blocks (e.g. a getBlocks result,
+-- Peer.hs:309-344): txids, merkle roots and the header comparison, with the
+-- txids never leaving the device. A block is marshalled as its 80-byte header
+-- plus each tx's @runPutS . serialize@; block b owns txs
+-- [offsets[b], offsets[b+1]) of the batch.
+checkBlocksBatch :: Verifier -> [Block] -> IO [BlockCheck]
+checkBlocksBatch _ [] = return []
+checkBlocksBatch v blocks = withMVar v.lock $ \_ ->
+  withRawTxs (concatMap (map (runPutS . serialize) . (.txs)) blocks) $ \ptxs ->
+    BU.unsafeUseAsCString (B.concat (map (runPutS . serialize . (.header)) blocks)) $ \phdrs ->
+      withArray (scanl (+) 0 (map (fromIntegral . length . (.txs)) blocks) :: [Word32]) $ \pboffs ->
+        allocaArray (32 * nb) $ \roots ->
+          allocaArray nb $ \st -> do
+            c_hkv_check_blocks v.ctx ptxs pboffs (fromIntegral nb) (castPtr phdrs) nullPtr roots st
+              >>= check "hkv_check_blocks" . fromIntegral
+            flags <- peekArray nb st
+            when (any ((/= 0) . (.&. hkvBlkBadTx)) flags) $
+              throwIO (VerifierException "hkv_check_blocks: a serialised tx did not parse" (-1))
+            rs <- mapM (\i -> B.packCStringLen (castPtr roots `plusPtr` (32 * i), 32)) [0 .. nb - 1]
+            return
+              [ BlockCheck (f .&. hkvBlkMerkleOk /= 0) (f .&. hkvBlkMutated /= 0) (f .&. hkvBlkEmpty /= 0) r
+                | (f, r) <- zip flags rs
+              ]
+  where
+    nb = length blocks
 
 -- ---------------------------------------------------------------------------
 -- The Verify actor (withChain idiom, Chain.hs:277-307)

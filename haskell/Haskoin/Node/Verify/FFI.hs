@@ -28,6 +28,8 @@ module Haskoin.Node.Verify.FFI
     c_hkv_device_healthy,
     c_hkv_check_headers,
     c_hkv_merkle_roots,
+    c_hkv_tx_ids,
+    c_hkv_check_blocks,
     c_hkv_strerror,
     hkvLibsecp,
     hkvHaskoin,
@@ -35,6 +37,11 @@ module Haskoin.Node.Verify.FFI
     hkvNoForkId,
     hkvEInternal,
     hkvStatusTailFault,
+    hkvTxidBadTx,
+    hkvBlkMerkleOk,
+    hkvBlkMutated,
+    hkvBlkBadTx,
+    hkvBlkEmpty,
   )
 where
 
@@ -125,6 +132,21 @@ hkvEInternal = -5
 hkvStatusTailFault :: Word32
 hkvStatusTailFault = 1
 
+-- | HKV_TXID_BAD_TX: the per-tx status of a tx that does not parse (its txid
+-- is 32 zero bytes).
+hkvTxidBadTx :: Word8
+hkvTxidBadTx = 1
+
+-- | HKV_BLK_* flags of hkv_check_blocks' per-block status byte.
+hkvBlkMerkleOk, hkvBlkMutated, hkvBlkBadTx, hkvBlkEmpty :: Word8
+hkvBlkMerkleOk = 0x01 -- header merkle == buildMerkleRoot (txHash <$> txs)
+
+hkvBlkMutated = 0x02 -- two equal hashes paired at some level (CVE-2012-2459)
+
+hkvBlkBadTx = 0x04 -- a tx of the block does not parse; MERKLE_OK is never set
+
+hkvBlkEmpty = 0x08 -- no tx; root all zero; MERKLE_OK is never set
+
 -- Context / batch lifetime: cheap, may use `unsafe`.
 foreign import ccall safe "hkv_open"
   c_hkv_open :: CInt -> Word32 -> Ptr (Ptr HkvCtx) -> IO CInt
@@ -172,6 +194,18 @@ foreign import ccall safe "hkv_check_headers"
 
 foreign import ccall safe "hkv_merkle_roots"
   c_hkv_merkle_roots :: Ptr HkvCtx -> Ptr Word8 -> Ptr Word32 -> CSize -> Ptr Word8 -> Ptr Word8 -> IO CInt
+
+-- txHash of every tx of a batch: txids_out n_tx * 32 bytes (digest order),
+-- status n_tx bytes or nullPtr.
+foreign import ccall safe "hkv_tx_ids"
+  c_hkv_tx_ids :: Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word8 -> Ptr Word8 -> IO CInt
+
+-- b.header.merkle == buildMerkleRoot (txHash <$> b.txs) for a batch of blocks:
+-- txs, block_offsets (n_blocks + 1 tx indices), n_blocks, headers (80 bytes
+-- each), txids_out / roots_out (or nullPtr), status (n_blocks bytes).
+foreign import ccall safe "hkv_check_blocks"
+  c_hkv_check_blocks ::
+    Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word32 -> CSize -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> Ptr Word8 -> IO CInt
 
 foreign import ccall unsafe "hkv_strerror"
   c_hkv_strerror :: CInt -> IO CString

@@ -722,7 +722,7 @@ int stage_txs(DevCtx& d, const hkv_txs* h, const void* jobs, size_t job_bytes, h
 
 extern "C" {
 
-uint32_t hkv_version(void) { return (1u << 16) | 0u; }
+uint32_t hkv_version(void) { return (1u << 16) | 1u; }
 
 const char* hkv_strerror(int err) {
   switch (err) {
@@ -1430,6 +1430,116 @@ int hkv_merkle_roots(hkv_ctx* ctx, const uint8_t* txids, const uint32_t* offsets
   HKV_TRY(hipMemcpyAsync(roots_out, dr, n_blocks * 32, hipMemcpyDeviceToHost, d.stream), "D2H merkle roots");
   HKV_TRY(hipMemcpyAsync(mutated, dm, n_blocks, hipMemcpyDeviceToHost, d.stream), "D2H merkle mutated");
   HKV_TRY(hipStreamSynchronize(d.stream), "merkle sync");
+  return scratch_release(d, d.stream);
+}
+
+// ---- txHash and whole-block merkle checks -----------------------------------
+
+// a host batch's offsets must not decrease: tx t is then inside the
+// offsets[n_tx] bytes that are staged, whatever it holds
+static bool tx_offsets_sorted(const hkv_txs* t) {
+  for (uint32_t k = 0; k < t->n_tx; ++k)
+    if (t->offsets[k + 1] < t->offsets[k]) return false;
+  return true;
+}
+
+int hkv_tx_ids_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, uint8_t* d_txids, uint8_t* d_status,
+                      void* hip_stream) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size() || !txs_ok(d_txs)) return HKV_E_ARG;
+  if (d_txs->n_tx == 0) return HKV_OK;
+  if (!d_txids || !aligned(d_txids, 16) || !aligned(d_txs->offsets, 4)) return HKV_E_ARG;
+  DevCtx& d = ctx->devs[dev];
+  HKV_TRY(hipSetDevice(d.device), "hipSetDevice");
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);  // NULL: the null (default) stream (include/hkv.h)
+  HKV_TRY(hkv::launch_txids(d_txs->bytes, d_txs->offsets, d_txs->n_tx, d_txids, d_status, st), "txid launch");
+  return HKV_OK;
+}
+
+int hkv_tx_ids(hkv_ctx* ctx, const hkv_txs* txs, uint8_t* txids_out, uint8_t* status) {
+  if (!ctx || ctx->devs.empty() || !txs_ok(txs)) return HKV_E_ARG;
+  const size_t n = txs->n_tx;
+  if (n == 0) return HKV_OK;
+  if (!txids_out || !tx_offsets_sorted(txs)) return HKV_E_ARG;
+  std::lock_guard<std::mutex> txl(*ctx->tx_mu[0]);  // (the tx staging of device 0)
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DevCtx& d = ctx->devs[0];
+  HKV_TRY(hipSetDevice(d.device), "hipSetDevice");
+  hkv_txs in = *txs, dt;  // the scripts pool is not read: not staged
+  in.scripts = nullptr;
+  in.scripts_len = 0;
+  void* unused = nullptr;
+  int rc = scratch_acquire(d, d.stream);
+  if (!rc) rc = stage_txs(d, &in, nullptr, 0, &dt, &unused);
+  if (!rc) rc = grow(&d.stage[4], &d.stage_cap[4], n * 33, "hipMalloc(txid out)");
+  if (rc) return rc;
+  uint8_t* dout = static_cast<uint8_t*>(d.stage[4]);
+  HKV_TRY(hkv::launch_txids(dt.bytes, dt.offsets, dt.n_tx, dout, dout + n * 32, d.stream), "txid launch");
+  HKV_TRY(hipMemcpyAsync(txids_out, dout, n * 32, hipMemcpyDeviceToHost, d.stream), "D2H txids");
+  if (status) HKV_TRY(hipMemcpyAsync(status, dout + n * 32, n, hipMemcpyDeviceToHost, d.stream), "D2H txid status");
+  HKV_TRY(hipStreamSynchronize(d.stream), "txid sync");
+  return scratch_release(d, d.stream);
+}
+
+int hkv_check_blocks_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_block_offsets,
+                            size_t n_blocks, const uint8_t* d_headers, uint8_t* d_txids, uint8_t* d_scratch,
+                            uint8_t* d_roots, uint8_t* d_mutated, uint8_t* d_status, void* hip_stream) {
+  if (!ctx || dev < 0 || dev >= (int)ctx->devs.size() || !txs_ok(d_txs) || n_blocks > 0x7FFFFFFFull) return HKV_E_ARG;
+  if (n_blocks == 0) return HKV_OK;
+  if (!d_block_offsets || !d_headers || !d_txids || !d_scratch || !d_roots || !d_mutated || !d_status ||
+      !aligned(d_txids, 16) || !aligned(d_scratch, 16) || !aligned(d_roots, 16) || !aligned(d_block_offsets, 4) ||
+      !aligned(d_headers, 4) || !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  DevCtx& d = ctx->devs[dev];
+  HKV_TRY(hipSetDevice(d.device), "hipSetDevice");
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);  // NULL: the null (default) stream (include/hkv.h)
+  HKV_TRY(hkv::launch_txids(d_txs->bytes, d_txs->offsets, d_txs->n_tx, d_txids, nullptr, st), "txid launch");
+  HKV_TRY(hkv::launch_merkle(d_txids, d_block_offsets, (uint32_t)n_blocks, d_scratch, d_roots, d_mutated,
+                             (uint32_t)d.n_cu, st),
+          "merkle launch");
+  HKV_TRY(hkv::launch_block_verdicts(d_txids, d_block_offsets, (uint32_t)n_blocks, d_headers, d_roots, d_mutated,
+                                     d_status, st),
+          "block verdict launch");
+  return HKV_OK;
+}
+
+int hkv_check_blocks(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* block_offsets, size_t n_blocks,
+                     const uint8_t* headers, uint8_t* txids_out, uint8_t* roots_out, uint8_t* status) {
+  if (!ctx || ctx->devs.empty() || !txs_ok(txs) || n_blocks > 0x7FFFFFFFull) return HKV_E_ARG;
+  if (n_blocks == 0) return HKV_OK;
+  if (!block_offsets || !headers || !status || block_offsets[0] != 0) return HKV_E_ARG;
+  for (size_t b = 0; b < n_blocks; ++b)
+    if (block_offsets[b + 1] < block_offsets[b]) return HKV_E_ARG;
+  const size_t n = txs->n_tx;
+  if (block_offsets[n_blocks] > n || !tx_offsets_sorted(txs)) return HKV_E_ARG;
+  std::lock_guard<std::mutex> txl(*ctx->tx_mu[0]);  // (the tx staging of device 0)
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DevCtx& d = ctx->devs[0];
+  HKV_TRY(hipSetDevice(d.device), "hipSetDevice");
+  hkv_txs in = *txs, dt;  // the scripts pool is not read: not staged
+  in.scripts = nullptr;
+  in.scripts_len = 0;
+  void* unused = nullptr;
+  // one staging buffer beside the tx staging:
+  // txids (n*32) | scratch (n*32) | roots (B*32) | headers (B*80) | offsets ((B+1)*4) | mutated (B) | status (B)
+  const size_t off_bytes = (n_blocks + 1) * 4;
+  int rc = scratch_acquire(d, d.stream);
+  if (!rc) rc = stage_txs(d, &in, nullptr, 0, &dt, &unused);
+  if (!rc) rc = grow(&d.stage[6], &d.stage_cap[6], n * 64 + n_blocks * 114 + off_bytes, "hipMalloc(block batch)");
+  if (rc) return rc;
+  uint8_t* b = static_cast<uint8_t*>(d.stage[6]);
+  uint8_t *dl = b, *dsc = dl + n * 32, *dr = dsc + n * 32, *dh = dr + n_blocks * 32, *doff = dh + n_blocks * 80,
+          *dm = doff + off_bytes, *dst = dm + n_blocks;
+  HKV_TRY(hipMemcpyAsync(dh, headers, n_blocks * 80, hipMemcpyHostToDevice, d.stream), "H2D block headers");
+  HKV_TRY(hipMemcpyAsync(doff, block_offsets, off_bytes, hipMemcpyHostToDevice, d.stream), "H2D block offsets");
+  const uint32_t* doff32 = reinterpret_cast<const uint32_t*>(doff);
+  HKV_TRY(hkv::launch_txids(dt.bytes, dt.offsets, dt.n_tx, dl, nullptr, d.stream), "txid launch");
+  HKV_TRY(hkv::launch_merkle(dl, doff32, (uint32_t)n_blocks, dsc, dr, dm, (uint32_t)d.n_cu, d.stream), "merkle launch");
+  HKV_TRY(hkv::launch_block_verdicts(dl, doff32, (uint32_t)n_blocks, dh, dr, dm, dst, d.stream),
+          "block verdict launch");
+  if (txids_out && n) HKV_TRY(hipMemcpyAsync(txids_out, dl, n * 32, hipMemcpyDeviceToHost, d.stream), "D2H txids");
+  if (roots_out) HKV_TRY(hipMemcpyAsync(roots_out, dr, n_blocks * 32, hipMemcpyDeviceToHost, d.stream), "D2H roots");
+  HKV_TRY(hipMemcpyAsync(status, dst, n_blocks, hipMemcpyDeviceToHost, d.stream), "D2H block status");
+  HKV_TRY(hipStreamSynchronize(d.stream), "block check sync");
   return scratch_release(d, d.stream);
 }
 

@@ -382,6 +382,54 @@ hipError_t launch_merkle(const uint8_t* leaves, const uint32_t* offsets, uint32_
   return hipGetLastError();
 }
 
+// Whole-block verdicts (the reference's block assertion, NodeSpec.hs:185-193:
+// b.header.merkle == buildMerkleRoot (txHash <$> b.txs)), after hkv_txid_kernel
+// and the merkle kernels: one wave per block. The lanes stride the block's
+// txids looking for one that hkv_txid_kernel rejected. Such a tx is known by
+// its all-zero txid, which is what that kernel defines for it and what no
+// SHA-256d of a parsed tx gives, so the block entry points need no per-tx
+// status buffer. Lane 0 then compares the root with header bytes [36,68)
+// (both in digest order) and folds in the mutated byte.
+__global__ void __launch_bounds__(64) hkv_block_verdict_kernel(const uint32_t* __restrict__ txids,
+                                                               const uint32_t* __restrict__ offsets,
+                                                               const uint32_t* __restrict__ hdrs,
+                                                               const uint32_t* __restrict__ roots,
+                                                               const uint8_t* __restrict__ mutated,
+                                                               uint8_t* __restrict__ status) {
+  const uint32_t blk = blockIdx.x;
+  const uint32_t off = offsets[blk], end = offsets[blk + 1];
+  int bad = 0;
+  for (uint32_t i = off + threadIdx.x; i < end; i += 64) {
+    uint32_t v[8];
+    load8(v, txids + (size_t)i * 8);
+    bad |= (v[0] | v[1] | v[2] | v[3] | v[4] | v[5] | v[6] | v[7]) == 0;
+  }
+  bad = __any(bad);
+  if (threadIdx.x == 0) {
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) diff |= hdrs[(size_t)blk * 20 + 9 + k] ^ roots[(size_t)blk * 8 + k];
+    uint32_t st = 0;
+    if (end <= off) {
+      st = HKV_BLK_EMPTY;
+    } else {
+      if (bad) st |= HKV_BLK_BAD_TX;
+      else if (diff == 0) st |= HKV_BLK_MERKLE_OK;
+      if (mutated[blk]) st |= HKV_BLK_MUTATED;
+    }
+    status[blk] = (uint8_t)st;
+  }
+}
+
+hipError_t launch_block_verdicts(const uint8_t* txids, const uint32_t* offsets, uint32_t n_blocks, const uint8_t* hdrs,
+                                 const uint8_t* roots, const uint8_t* mutated, uint8_t* status, hipStream_t st) {
+  if (n_blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(hkv_block_verdict_kernel, dim3(n_blocks), dim3(64), 0, st,
+                     reinterpret_cast<const uint32_t*>(txids), offsets, reinterpret_cast<const uint32_t*>(hdrs),
+                     reinterpret_cast<const uint32_t*>(roots), mutated, status);
+  return hipGetLastError();
+}
+
 hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_limit, const uint8_t* prev0,
                           uint8_t* hashes, uint8_t* status, hipStream_t st) {
   if (n == 0) return hipSuccess;

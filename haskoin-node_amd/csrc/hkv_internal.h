@@ -130,6 +130,9 @@ hipError_t launch_sighash(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt
 hipError_t launch_std_inputs(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
                              uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, int32_t forkid,
                              uint8_t* recs, hipStream_t st);
+// txHash of every tx (txids: n_tx * 32 bytes, 16-aligned; status: n_tx bytes or null)
+hipError_t launch_txids(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, uint8_t* txids, uint8_t* status,
+                        hipStream_t st);
 // the overlapped extraction of large batches: the BIP143 per-tx hashes alone
 // (rows written by launch_tx_index(TX_HASHES_NONE) before)
 hipError_t launch_tx_hashes_only(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, uint32_t hashes,
@@ -143,4 +146,7 @@ hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_li
                           uint8_t* hashes, uint8_t* status, hipStream_t st);
 hipError_t launch_merkle(const uint8_t* leaves, const uint32_t* offsets, uint32_t n_blocks, uint8_t* scratch,
                          uint8_t* roots, uint8_t* mutated, uint32_t n_cu, hipStream_t st);
+// per block: header merkle field == computed root, the mutated flag, rejected txs (HKV_BLK_*)
+hipError_t launch_block_verdicts(const uint8_t* txids, const uint32_t* offsets, uint32_t n_blocks, const uint8_t* hdrs,
+                                 const uint8_t* roots, const uint8_t* mutated, uint8_t* status, hipStream_t st);
 }  // namespace hkv

@@ -149,9 +149,17 @@ HKV_DEV void gen_clear(Gen& g) {
   g.code = nullptr; g.code_len = g.code_out = g.ccur = 0; g.value = 0;
   g.hp = g.hs = g.ho = nullptr;
 }
-HKV_DEV void piece_copy(Gen& g, const uint8_t* p, uint32_t n) { g.src = p; g.rem = n; }
-HKV_DEV void piece_lit(Gen& g, uint64_t v, uint32_t n) { g.src = nullptr; g.lit = v; g.rem = n; }
-HKV_DEV void piece_varint(Gen& g, uint32_t v) {
+// The piece setters, gen_more / gen_next / gen_word and sha256_stream are
+// templates over the generator: Gen here, and hkv_sighash.hip's TxGen (txHash),
+// a type of its own so that this switch, and with it every kernel that
+// instantiates it, stays as it is. A generator has src / lit / rem / phase
+// (PH_DONE = 0 ends it) and a gen_advance overload.
+template <class G>
+HKV_DEV void piece_copy(G& g, const uint8_t* p, uint32_t n) { g.src = p; g.rem = n; }
+template <class G>
+HKV_DEV void piece_lit(G& g, uint64_t v, uint32_t n) { g.src = nullptr; g.lit = v; g.rem = n; }
+template <class G>
+HKV_DEV void piece_varint(G& g, uint32_t v) {
   uint32_t n;
   const uint64_t l = varint_lit(v, n);
   piece_lit(g, l, n);
@@ -333,11 +341,13 @@ HKV_DEV void gen_advance(Gen& g) {
   }
 }
 
-HKV_DEV bool gen_more(Gen& g) {
+template <class G>
+HKV_DEV bool gen_more(G& g) {
   while (g.rem == 0 && g.phase != PH_DONE) gen_advance(g);
   return g.rem != 0;
 }
-HKV_DEV uint32_t gen_next(Gen& g) {
+template <class G>
+HKV_DEV uint32_t gen_next(G& g) {
   uint32_t b;
   if (g.src) {
     b = *g.src;
@@ -366,7 +376,8 @@ static inline uint32_t xtpb_for(size_t n) { return n <= HKV_XSMALL ? 64u : (uint
 // piece the 4 bytes come from 4 independent loads (or the literal's next
 // 32 bits) instead of 4 dependent load / store rounds; piece boundaries take
 // the byte path.
-HKV_DEV uint32_t gen_word(Gen& g, uint32_t& w) {
+template <class G>
+HKV_DEV uint32_t gen_word(G& g, uint32_t& w) {
   if (g.rem >= 4u) {
     if (g.src) {
       const uint8_t* s = g.src;
@@ -393,7 +404,8 @@ HKV_DEV uint32_t gen_word(Gen& g, uint32_t& w) {
 // iteration every live lane writes its next 64 bytes (message, then 0x80,
 // zeros and the 64-bit length) into its LDS slot buf[word * WG + tid] and all
 // of them compress together. Call from wave-uniform control flow.
-HKV_DEV void sha256_stream(uint32_t h[8], Gen& g, bool live, uint32_t* buf) {
+template <class G>
+HKV_DEV void sha256_stream(uint32_t h[8], G& g, bool live, uint32_t* buf) {
   sha256_init(h);
   const uint32_t tid = threadIdx.x;
   // word at a time: 16 LDS word stores per block; 0x80 right after the last

@@ -5,11 +5,13 @@ This is the Python face of the product path; it loads the in-tree
 ``haskoin-node_amd/lib/libhkv.so`` (built by ``__graft_entry__.build()``)
 and fails loudly when it is missing. There is no CPU fallback.
 """
-from .lib import (HKV_HASKOIN, HKV_LIBSECP, HKV_NO_FORKID, HKV_RECORD_SIZE, HKV_SIGHASH_FORKID,
-                  HKV_SIGHASH_LEGACY, HkvError, HkvTxs, lib_path, load_library)
+from .lib import (HKV_BLK_BAD_TX, HKV_BLK_EMPTY, HKV_BLK_MERKLE_OK, HKV_BLK_MUTATED, HKV_HASKOIN, HKV_LIBSECP,
+                  HKV_NO_FORKID, HKV_RECORD_SIZE, HKV_SIGHASH_FORKID, HKV_SIGHASH_LEGACY, HKV_TXID_BAD_TX,
+                  HKV_TXID_OK, HkvError, HkvTxs, lib_path, load_library)
 from .records import make_record, pack_records, unpack_bits
 from .headers import check_headers, check_headers_device
 from .merkle import merkle_roots, merkle_roots_device
+from .blocks import check_blocks, check_blocks_device, split_block, tx_ids, tx_ids_device
 from .sighash import TxBatch, tx_sig_hash_batch, verify_std_inputs
 from .verify import (Verifier, VerifierConfig, verify_hash_sig_batch,
                      verify_raw_batch)
@@ -22,4 +24,6 @@ __all__ = [
     "HKV_SIGHASH_FORKID", "HKV_SIGHASH_LEGACY", "HkvTxs", "TxBatch", "tx_sig_hash_batch",
     "verify_std_inputs", "check_headers", "check_headers_device",
     "merkle_roots", "merkle_roots_device", "VerifyActor", "VerifyActorConfig",
+    "tx_ids", "tx_ids_device", "split_block", "check_blocks", "check_blocks_device",
+    "HKV_TXID_OK", "HKV_TXID_BAD_TX", "HKV_BLK_MERKLE_OK", "HKV_BLK_MUTATED", "HKV_BLK_BAD_TX", "HKV_BLK_EMPTY",
 ]

@@ -19,6 +19,9 @@ HKV_SH_OK, HKV_SH_BAD_TX, HKV_SH_BAD_INPUT, HKV_SH_BAD_REF = 0, 1, 2, 3
 HKV_HDR_POW_OK, HKV_HDR_LINK_OK, HKV_HDR_NEGATIVE, HKV_HDR_OVERFLOW = 0x01, 0x02, 0x04, 0x08
 HKV_HDR_ZERO_TARGET, HKV_HDR_ABOVE_LIMIT, HKV_HDR_HASH_ABOVE = 0x10, 0x20, 0x40
 
+HKV_TXID_OK, HKV_TXID_BAD_TX = 0, 1
+HKV_BLK_MERKLE_OK, HKV_BLK_MUTATED, HKV_BLK_BAD_TX, HKV_BLK_EMPTY = 0x01, 0x02, 0x04, 0x08
+
 HKV_OK = 0
 HKV_FAIL_NONE, HKV_FAIL_ENQUEUE, HKV_FAIL_JOIN, HKV_FAIL_ALLOC, HKV_FAIL_TAIL = 0, 1, 2, 3, 4
 HKV_STATUS_TAIL_FAULT = 1
@@ -100,6 +103,12 @@ EXPORTS = {
     "hkv_merkle_roots": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "hkv_merkle_roots_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "hkv_tx_ids": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_void_p]),
+    "hkv_tx_ids_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p]),
+    "hkv_check_blocks": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "hkv_check_blocks_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_size_t, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hkv_check_headers": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hkv_check_headers_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),

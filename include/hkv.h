@@ -37,6 +37,13 @@
  *       replaces the per-header part of haskoin-core `connectBlocks` reached
  *       from importHeaders (/root/reference/src/Haskoin/Node/Chain.hs:500-520):
  *       headerHash, isValidPOW (decodeCompact) and the prev-hash link.
+ *   hkv_tx_ids / hkv_tx_ids_device
+ *       replaces N calls of haskoin-core `txHash :: Tx -> TxHash`
+ *       (SHA-256d of the tx re-serialised without witness data).
+ *   hkv_check_blocks / hkv_check_blocks_device
+ *       replaces the reference's block assertion on getBlocks results
+ *       (Peer.hs:309-344; test/Haskoin/NodeSpec.hs:185-193):
+ *       b.header.merkle == buildMerkleRoot (txHash <$> b.txs), per block.
  *
  * Streams: device-form calls enqueue on the caller's stream; calls on one
  * device share its scratch buffers, so each call is ordered after the
@@ -358,6 +365,66 @@ int hkv_merkle_roots(hkv_ctx* ctx, const uint8_t* txids, const uint32_t* offsets
 int hkv_merkle_roots_device(hkv_ctx* ctx, int dev, const uint8_t* d_txids, const uint32_t* d_offsets,
                             size_t n_blocks, uint8_t* d_scratch, uint8_t* d_roots, uint8_t* d_mutated,
                             void* hip_stream);
+
+/* ---------------------------------------------------------------------------
+ * Transaction hashes and whole-block merkle checks.
+ *
+ * hkv_tx_ids / hkv_tx_ids_device replace N calls of haskoin-core
+ * `txHash :: Tx -> TxHash` [dep, haskoin-core-1.1.0 Haskoin.Transaction.Common]
+ * = doubleSHA256 (runPutS (serialize tx{witness = []})): the hash of the
+ * decoded and re-serialised tx, not of its wire bytes. The segwit marker and
+ * flag and every witness stack are dropped, and the varints haskoin
+ * re-serialises (input count, scriptSig lengths, output count, output script
+ * lengths) are re-emitted canonically, as in hkv_sighash. The 32 bytes are in
+ * digest order, the order hkv_merkle_roots takes and header bytes [36,68)
+ * hold. A tx that does not parse (it does not fill its [offsets[t],
+ * offsets[t+1]) range exactly, is truncated, is shorter than 10 bytes or has a
+ * count or length >= 2^32) gets an all-zero txid and status HKV_TXID_BAD_TX.
+ * wtxids and the BIP141 witness commitment are not computed.
+ * ------------------------------------------------------------------------ */
+#define HKV_TXID_OK 0u
+#define HKV_TXID_BAD_TX 1u
+/* txHash of every tx of the batch (scripts pool unused, may be NULL/0).
+ * txids_out: n_tx * 32 bytes, digest order; status: n_tx bytes or NULL.
+ * Host memory, first device, blocking; offsets must be non-decreasing
+ * (HKV_E_ARG). */
+int hkv_tx_ids(hkv_ctx* ctx, const hkv_txs* txs, uint8_t* txids_out, uint8_t* status);
+/* Device form: every pointer (those of d_txs included) in HBM of device
+ * `dev`; d_txids 16-byte aligned; d_status n_tx bytes or NULL. Enqueued on
+ * hip_stream, not synchronised. Stateless: it uses none of the device's
+ * scratch, so it is not ordered against other calls on the device. */
+int hkv_tx_ids_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, uint8_t* d_txids, uint8_t* d_status,
+                      void* hip_stream);
+
+/* hkv_check_blocks / hkv_check_blocks_device replace, for a batch of blocks,
+ * the reference's block assertion on getBlocks results
+ * (test/Haskoin/NodeSpec.hs:185-193 on blocks from src/Haskoin/Node/Peer.hs:309-344):
+ *   b.header.merkle == buildMerkleRoot (txHash <$> b.txs)
+ * as hkv_tx_ids, then hkv_merkle_roots, then the comparison with header bytes
+ * [36,68), without the txids leaving the device. Per-block status flags: */
+#define HKV_BLK_MERKLE_OK 0x01u /* header merkle == buildMerkleRoot (txHash <$> txs) */
+#define HKV_BLK_MUTATED 0x02u   /* two equal hashes paired at some level (CVE-2012-2459) */
+#define HKV_BLK_BAD_TX 0x04u    /* a tx of the block does not parse; MERKLE_OK is never set */
+#define HKV_BLK_EMPTY 0x08u     /* no tx; root all zero; MERKLE_OK is never set */
+/* Block b owns txs [block_offsets[b], block_offsets[b+1]) of the batch
+ * (n_blocks + 1 tx indices, block_offsets[0] == 0, non-decreasing, last <= n_tx;
+ * HKV_E_ARG otherwise); headers: n_blocks * 80 wire bytes. txids_out (n_tx*32)
+ * and roots_out (n_blocks*32) may be NULL in the host form; status: n_blocks
+ * bytes. The root of a block with a tx that does not parse is computed over
+ * the txids as written, that tx's 32 zero bytes included (two such txs paired
+ * in the tree also set HKV_BLK_MUTATED): HKV_BLK_BAD_TX is the verdict, the root
+ * means nothing. Host memory, first device, blocking. */
+int hkv_check_blocks(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* block_offsets, size_t n_blocks,
+                     const uint8_t* headers, uint8_t* txids_out, uint8_t* roots_out, uint8_t* status);
+/* Device form: every pointer in HBM of device `dev`, none NULL; d_txids and
+ * d_scratch n_tx * 32 bytes each, 16-byte aligned as d_roots (n_blocks * 32),
+ * d_scratch aliasing nothing else; d_headers and d_block_offsets 4-byte
+ * aligned; d_mutated and d_status n_blocks bytes. The caller vouches for
+ * d_block_offsets. Enqueued on hip_stream, not synchronised; stateless as
+ * hkv_tx_ids_device. */
+int hkv_check_blocks_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_block_offsets,
+                            size_t n_blocks, const uint8_t* d_headers, uint8_t* d_txids, uint8_t* d_scratch,
+                            uint8_t* d_roots, uint8_t* d_mutated, uint8_t* d_status, void* hip_stream);
 
 /* Synthetic-data hooks (block-mix generator, off the verify path):
  * n random private keys -> d_priv (n*32, big-endian), compressed public keys
