@@ -22,6 +22,55 @@ enum {
   HKV_DBG_ECMULT_G = 10,
   HKV_DBG_MUL512 = 11,
   HKV_DBG_SQR512 = 12,
+  // Lane i takes row i of a and of b; "next" is row (i + 1) mod n. Field
+  // results come back raw (weak form) in out[0..8) and normalised in
+  // out[8..16) — ops 1..4 keep their normalised out[0..8) and add the raw form
+  // in out[8..16) — paired ops return their two results normalised in
+  // out[0..8) and out[8..16), predicates 0 or 1 in out[0].
+  HKV_DBG_FE_CNEG = 13,        // neg = bit 0 of b's low limb
+  HKV_DBG_FE_CNEG_MASK = 14,   // mask = all ones when bit 0 of b's low limb is set
+  HKV_DBG_FE_NEG = 15,
+  HKV_DBG_FE_HALF = 16,
+  HKV_DBG_FE_SHL = 17,         // s = b's low limb (1..31); s = 1 is the compile-time shift of the group formulas
+  HKV_DBG_FE_SHL_VAR = 18,     // s = b's low limb (1..31)
+  HKV_DBG_FE_MUL_SMALL = 19,   // k = b's low limb (< 2^16)
+  HKV_DBG_FE_MUL_SMALL2 = 20,  // (a * k1, next a * k2): k1, k2 = limbs 0, 1 of b (<= 2^8)
+  // fe_lin2 has four inputs and a and b are full 256-bit operands, so the
+  // per-lane constants ride in the next row: its b's low 16 bits. A test
+  // that wants a given (ka, kb) in lane i forces those bits of row i + 1's b
+  // (tests/field_cases.py lin2_rows builds such rows).
+  HKV_DBG_FE_LIN2 = 21,        // ka a - kb b: ka, kb = bytes 0, 1 of next b's low limb
+  HKV_DBG_FE_MUL_ADD = 22,     // a b + next a
+  HKV_DBG_FE_MUL2 = 23,        // (a b, next a * next b)
+  HKV_DBG_FE_SQR2 = 24,        // (a^2, b^2)
+  HKV_DBG_FE_SQRMUL = 25,      // (a^2, b * next a)
+  HKV_DBG_FE_MUL_REF = 26,
+  HKV_DBG_FE_SQR_REF = 27,
+  HKV_DBG_FE_NORMALIZE = 28,   // out[0..8) = a normalised
+  HKV_DBG_FE_IS_ZERO = 29,
+  HKV_DBG_FE_EQUAL = 30,
+  HKV_DBG_U256_LT_P = 31,
+  HKV_DBG_SC_ADD = 32,         // scalar results in out[0..8)
+  HKV_DBG_SC_SUB = 33,
+  HKV_DBG_SC_NEG = 34,
+  HKV_DBG_SC_SQR = 35,
+  HKV_DBG_SC_IS_HIGH = 36,
+  HKV_DBG_INV_MOD_P = 37,      // sgcd::inv_mod_p (a < p; 0 gives 0), out[0..8)
+  // Group ops (hkv_debug_group_kernel): lane i takes rows 2i and 2i + 1 (n
+  // even, n / 2 lanes). a: k1 | z1, b: k2 | w. The lane's points are
+  // P1 = k1 G and P2 = k2 G (ecmult_simple; a zero scalar is infinity), P1
+  // lifted to Jacobian (x z1^2, y z1^3, z1). Selector bits, in w's low limb:
+  // 1 = take, 2 = the accumulator is infinity on entry, 4 = b is infinity.
+  // out row 2i = the affine result x | y (all zero for infinity), out row
+  // 2i + 1 = {infinity flag, ...}.
+  HKV_DBG_GEJ_DOUBLE = 64,               // 2 P1
+  HKV_DBG_GEJ_DOUBLE_ILP = 65,
+  HKV_DBG_GEJ_ACCUMULATE = 66,           // (P1, inf) += P2 under take; a lane at infinity stays there
+  HKV_DBG_GEJ_ACCUMULATE_ILP = 67,
+  HKV_DBG_GEJ_ADD_VAR = 68,              // (P1, inf) += (P2 lifted with z = w, binf)
+  HKV_DBG_GEJ_ADD_AFFINE_COMPLETE = 69,  // (P1, inf) += P2 under take
+  HKV_DBG_X_MATCHES_R = 70,              // x_matches_r(k1 z1^2, z1, k2): k1 is x and k2 is r as given; out[0]
+  HKV_DBG_ECMULT = 71,                   // ecmult_simple(k1, k2, z1 G): z1 is the scalar of P
 };
 
 namespace hkv {

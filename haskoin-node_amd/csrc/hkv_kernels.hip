@@ -2519,11 +2519,37 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
   uint32_t res[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) res[k] = 0;
+  // the third operands: row (i + 1) mod n
+  const uint32_t inext = (i + 1 == n) ? 0u : i + 1;
+  auto load_next = [&](fe& r, const uint32_t* __restrict__ src) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.v[k] = src[inext * 8 + k];
+  };
+  auto raw_norm = [&](fe& r) {  // raw | normalised
+#pragma unroll
+    for (int k = 0; k < 8; ++k) res[k] = r.v[k];
+    fe_normalize(r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) res[8 + k] = r.v[k];
+  };
+  auto norm_raw = [&](fe& r) {  // normalised | raw (ops 1..4)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) res[8 + k] = r.v[k];
+    fe_normalize(r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) res[k] = r.v[k];
+  };
+  auto norm_pair = [&](fe& r1, fe& r2) {
+    fe_normalize(r1);
+    fe_normalize(r2);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { res[k] = r1.v[k]; res[8 + k] = r2.v[k]; }
+  };
   switch (op) {
-    case HKV_DBG_FE_MUL: fe_mul(z, x, y); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
-    case HKV_DBG_FE_SQR: fe_sqr(z, x); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
-    case HKV_DBG_FE_ADD: fe_add(z, x, y); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
-    case HKV_DBG_FE_SUB: fe_sub(z, x, y); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
+    case HKV_DBG_FE_MUL: fe_mul(z, x, y); norm_raw(z); break;
+    case HKV_DBG_FE_SQR: fe_sqr(z, x); norm_raw(z); break;
+    case HKV_DBG_FE_ADD: fe_add(z, x, y); norm_raw(z); break;
+    case HKV_DBG_FE_SUB: fe_sub(z, x, y); norm_raw(z); break;
     case HKV_DBG_FE_INV: fe_inv(z, x); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
     case HKV_DBG_FE_SQRT: fe_sqrt_cand(z, x); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
     case HKV_DBG_SC_MUL: sc_mul(wres, u, v); for (int k = 0; k < 8; ++k) res[k] = wres.v[k]; break;
@@ -2548,10 +2574,177 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
     }
     case HKV_DBG_MUL512: mul512(res, x.v, y.v); break;
     case HKV_DBG_SQR512: sqr512(res, x.v); break;
+    case HKV_DBG_FE_CNEG: fe_cneg(z, x, (y.v[0] & 1u) != 0); raw_norm(z); break;
+    case HKV_DBG_FE_CNEG_MASK: fe_cneg_mask(z, x, 0u - (y.v[0] & 1u)); raw_norm(z); break;
+    case HKV_DBG_FE_NEG: fe_neg(z, x); raw_norm(z); break;
+    case HKV_DBG_FE_HALF: fe_half(z, x); raw_norm(z); break;
+    case HKV_DBG_FE_SHL: {
+      const uint32_t s = y.v[0];
+      if (s == 1u) fe_shl(z, x, 1);
+      else fe_shl(z, x, (int)s);
+      raw_norm(z);
+      break;
+    }
+    case HKV_DBG_FE_SHL_VAR: fe_shl_var(z, x, y.v[0]); raw_norm(z); break;
+    case HKV_DBG_FE_MUL_SMALL: fe_mul_small(z, x, y.v[0]); raw_norm(z); break;
+    case HKV_DBG_FE_MUL_SMALL2: {
+      fe xn, z2;
+      load_next(xn, a);
+      fe_mul_small2(z, x, y.v[0], z2, xn, y.v[1]);
+      norm_pair(z, z2);
+      break;
+    }
+    case HKV_DBG_FE_LIN2: {
+      const uint32_t kk = b[inext * 8];
+      fe_lin2(z, x, kk & 0xFFu, y, (kk >> 8) & 0xFFu);
+      raw_norm(z);
+      break;
+    }
+    case HKV_DBG_FE_MUL_ADD: {
+      fe xn;
+      load_next(xn, a);
+      fe_mul_add(z, x, y, xn);
+      raw_norm(z);
+      break;
+    }
+    case HKV_DBG_FE_MUL2: {
+      fe xn, yn, z2;
+      load_next(xn, a);
+      load_next(yn, b);
+      fe_mul2(z, x, y, z2, xn, yn);
+      norm_pair(z, z2);
+      break;
+    }
+    case HKV_DBG_FE_SQR2: {
+      fe z2;
+      fe_sqr2(z, x, z2, y);
+      norm_pair(z, z2);
+      break;
+    }
+    case HKV_DBG_FE_SQRMUL: {
+      fe xn, z2;
+      load_next(xn, a);
+      fe_sqrmul(z, x, z2, y, xn);
+      norm_pair(z, z2);
+      break;
+    }
+    case HKV_DBG_FE_MUL_REF: fe_mul_ref(z, x, y); raw_norm(z); break;
+    case HKV_DBG_FE_SQR_REF: fe_sqr_ref(z, x); raw_norm(z); break;
+    case HKV_DBG_FE_NORMALIZE: z = x; fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
+    case HKV_DBG_FE_IS_ZERO: res[0] = fe_is_zero(x) ? 1u : 0u; break;
+    case HKV_DBG_FE_EQUAL: res[0] = fe_equal(x, y) ? 1u : 0u; break;
+    case HKV_DBG_U256_LT_P: res[0] = u256_lt_p(x.v) ? 1u : 0u; break;
+    case HKV_DBG_SC_ADD: sc_add(wres, u, v); for (int k = 0; k < 8; ++k) res[k] = wres.v[k]; break;
+    case HKV_DBG_SC_SUB: sc_sub(wres, u, v); for (int k = 0; k < 8; ++k) res[k] = wres.v[k]; break;
+    case HKV_DBG_SC_NEG: sc_neg(wres, u); for (int k = 0; k < 8; ++k) res[k] = wres.v[k]; break;
+    case HKV_DBG_SC_SQR: sc_sqr(wres, u); for (int k = 0; k < 8; ++k) res[k] = wres.v[k]; break;
+    case HKV_DBG_SC_IS_HIGH: res[0] = sc_is_high(u) ? 1u : 0u; break;
+    case HKV_DBG_INV_MOD_P: sgcd::inv_mod_p(res, x.v); break;
     default: break;
   }
 #pragma unroll
   for (int k = 0; k < 16; ++k) out[i * 16 + k] = res[k];
+}
+
+// The group ops of the known-answer hook (hkv_internal.h): lane i takes rows
+// 2i and 2i + 1 of a (k1 | z1) and b (k2 | w), builds P1 = k1 G, P2 = k2 G with
+// ecmult_simple, lifts P1 to (x z1^2, y z1^3, z1), applies the op and returns
+// the affine result in out row 2i, the infinity flag in out row 2i + 1.
+__global__ void __launch_bounds__(WG) hkv_debug_group_kernel(uint32_t op, uint32_t lanes,
+                                                             const uint32_t* __restrict__ a,
+                                                             const uint32_t* __restrict__ b,
+                                                             uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= lanes) return;
+  sc k1, k2, zero;
+  fe z1, w;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    k1.v[k] = a[(2 * i) * 8 + k];
+    z1.v[k] = a[(2 * i + 1) * 8 + k];
+    k2.v[k] = b[(2 * i) * 8 + k];
+    w.v[k] = b[(2 * i + 1) * 8 + k];
+    zero.v[k] = 0;
+  }
+  const uint32_t sel = w.v[0];
+  const bool take = (sel & 1u) != 0;
+  ge g, p1, p2, o;
+  ge_set_g(g);
+  fe_set_zero(o.x);
+  fe_set_zero(o.y);
+  bool oinf = false;
+  uint32_t flag = 0;
+  if (op == HKV_DBG_X_MATCHES_R) {
+    fe X, zz, xin;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) xin.v[k] = k1.v[k];
+    fe_sqr(zz, z1);
+    fe_mul(X, xin, zz);
+    o.x.v[0] = x_matches_r(X, z1, k2.v) ? 1u : 0u;
+  } else if (op == HKV_DBG_ECMULT) {
+    sc kp;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) kp.v[k] = z1.v[k];
+    p1 = g;
+    const bool pok = ecmult_simple(p2, kp, zero, g);  // P (never infinity: the tests pass kp != 0)
+    if (!pok) p2 = g;
+    oinf = !ecmult_simple(p1, k1, k2, p2);
+    if (!oinf) o = p1;
+  } else {
+    p1 = g;
+    p2 = g;
+    ge t;
+    const bool ok1 = ecmult_simple(t, k1, zero, g);
+    if (ok1) p1 = t;
+    const bool ok2 = ecmult_simple(t, k2, zero, g);
+    if (ok2) p2 = t;
+    gej acc;
+    fe zz, zzz;
+    fe_sqr(zz, z1);
+    fe_mul(zzz, zz, z1);
+    fe_mul(acc.x, p1.x, zz);
+    fe_mul(acc.y, p1.y, zzz);
+    acc.z = z1;
+    bool inf = !ok1 || (sel & 2u) != 0;
+    switch (op) {
+      case HKV_DBG_GEJ_DOUBLE: gej_double(acc, acc); break;
+      case HKV_DBG_GEJ_DOUBLE_ILP: gej_double_ilp(acc, acc); break;
+      case HKV_DBG_GEJ_ACCUMULATE: gej_accumulate(acc, inf, acc.z, p2.x, p2.y, take); break;
+      case HKV_DBG_GEJ_ACCUMULATE_ILP: gej_accumulate_ilp(acc, inf, acc.z, p2.x, p2.y, take); break;
+      case HKV_DBG_GEJ_ADD_AFFINE_COMPLETE: gej_add_affine_complete(acc, inf, p2, take); break;
+      case HKV_DBG_GEJ_ADD_VAR: {
+        gej bj;
+        fe_sqr(zz, w);
+        fe_mul(zzz, zz, w);
+        fe_mul(bj.x, p2.x, zz);
+        fe_mul(bj.y, p2.y, zzz);
+        bj.z = w;
+        gej_add_var(acc, inf, bj, !ok2 || (sel & 4u) != 0);
+        break;
+      }
+      default: break;
+    }
+    oinf = inf;
+    if (!inf) {
+      fe zi, zi2, zi3;
+      fe_inv(zi, acc.z);
+      fe_sqr(zi2, zi);
+      fe_mul(zi3, zi2, zi);
+      fe_mul(o.x, acc.x, zi2);
+      fe_mul(o.y, acc.y, zi3);
+      fe_normalize(o.x);
+      fe_normalize(o.y);
+    }
+  }
+  flag = oinf ? 1u : 0u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    out[(2 * i) * 16 + k] = oinf ? 0u : o.x.v[k];
+    out[(2 * i) * 16 + 8 + k] = oinf ? 0u : o.y.v[k];
+  }
+  out[(2 * i + 1) * 16] = flag;
+#pragma unroll
+  for (int k = 1; k < 16; ++k) out[(2 * i + 1) * 16 + k] = 0;
 }
 
 }  // namespace hkv
@@ -2880,6 +3073,11 @@ hipError_t launch_gen_records(uint64_t seed, uint64_t index0, uint32_t n, const 
 }
 hipError_t launch_debug(uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* out,
                         hipStream_t st) {
+  if (op >= HKV_DBG_GEJ_DOUBLE) {  // two rows per lane
+    if (n < 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hkv_debug_group_kernel, dim3(ceil_div(n / 2, WG)), dim3(WG), 0, st, op, n / 2, a, b, out);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(hkv_debug_kernel, dim3(ceil_div(n, WG)), dim3(WG), 0, st, op, n, a, b, out);
   return hipGetLastError();
 }

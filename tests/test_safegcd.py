@@ -34,6 +34,12 @@ def binary_full(tmp_path_factory):
 
 P = 2**256 - 2**32 - 977
 
+# edge operands (also run on the device: test_gpu_primitives.py)
+LAMBDA = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
+EDGE_SCALARS = [1, 2, 3, N - 1, N - 2, (N - 1) // 2, (N + 1) // 2, 2**255, 2**128 - 1, 2**128, 2**128 + 1,
+                2**32 - 1, 2**30, 2**30 - 1, 2**60 + 1, LAMBDA, N - LAMBDA, 0x10364141, 2**256 - 2**224 - 1 - N]
+EDGE_FIELD = [1, 2, 3, P - 1, P - 2, (P - 1) // 2, 2**255, 2**32 + 977, 2**224, 0x3FFFFC2F, P - 2**32]
+
 
 def run(binary, xs, mod="n"):
     inp = "".join(f"{x:064x}\n" for x in xs)
@@ -42,10 +48,7 @@ def run(binary, xs, mod="n"):
 
 
 def test_safegcd_edge_scalars(binary):
-    lam = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
-    xs = [1, 2, 3, N - 1, N - 2, (N - 1) // 2, (N + 1) // 2, 2**255, 2**128 - 1, 2**128, 2**128 + 1,
-          2**32 - 1, 2**30, 2**30 - 1, 2**60 + 1, lam, N - lam, 0x10364141, 2**256 - 2**224 - 1 - N]
-    xs = [x % N for x in xs if x % N]
+    xs = [x % N for x in EDGE_SCALARS if x % N]
     for x, r in zip(xs, run(binary, xs)):
         assert r == pow(x, -1, N), hex(x)
 
@@ -65,7 +68,7 @@ def test_safegcd_zero_maps_to_zero(binary):
 
 def test_safegcd_mod_p(binary):
     rng = random.Random(0x50)
-    xs = [1, 2, 3, P - 1, P - 2, (P - 1) // 2, 2**255, 2**32 + 977, 2**224, 0x3FFFFC2F, P - 2**32]
+    xs = list(EDGE_FIELD)
     xs += [rng.randrange(1, P) for _ in range(20000)]
     xs += [rng.getrandbits(rng.randrange(1, 256)) or 1 for _ in range(3000)]
     xs += [P - (rng.getrandbits(rng.randrange(1, 128)) or 1) for _ in range(3000)]
