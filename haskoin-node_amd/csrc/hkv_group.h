@@ -15,6 +15,13 @@ namespace hkv {
 struct ge { fe x, y; };
 struct gej { fe x, y, z; };
 
+// 1: Y3 of gej_double, gej_add_ge_core and gej_accumulate as one sum scan
+// (fe_sqrmul_sum / fe_mul_sum: both products reduced once, then negated by
+// complement); 0: two reduced products and a subtraction.
+#ifndef HKV_SUM_SCANS
+#define HKV_SUM_SCANS 1
+#endif
+
 __constant__ static const uint32_t FE_GX[8] = {0x16F81798u, 0x59F2815Bu, 0x2DCE28D9u, 0x029BFCDBu,
                                                0xCE870B07u, 0x55A06295u, 0xF9DCBBACu, 0x79BE667Eu};
 __constant__ static const uint32_t FE_GY[8] = {0xFB10D4B8u, 0x9C47D08Fu, 0xA6855419u, 0xFD17B448u,
@@ -46,7 +53,24 @@ HKV_DEV void gej_cmov(gej& r, const gej& a, bool f) {
 // (-1.4% ecmult, profiles/r02_variants.log). On this ISA a product costs
 // about a square, so X*B beats the square-and-subtract form. a must not be
 // infinity; y != 0 on secp256k1. r may alias a.
+// With HKV_SUM_SCANS, -Y3' = B^2 + E'(X3' - M) is one sum scan (C is never
+// formed), negated by complement.
 HKV_DEV void gej_double(gej& r, const gej& a) {
+#if HKV_SUM_SCANS
+  fe A, B, M, E, t, u;
+  fe_sqr(A, a.x);
+  fe_sqr(B, a.y);
+  fe_mul(M, a.x, B);
+  fe_mul_small(E, A, 3);
+  fe_half(E, E);            // E' = 3A/2
+  fe_mul(r.z, a.y, a.z);    // Z3' = YZ
+  fe_sqr(t, E);
+  fe_shl(u, M, 1);
+  fe_sub(r.x, t, u);        // X3' = E'^2 - 2M
+  fe_sub(t, r.x, M);
+  fe_sqrmul_sum(t, B, E, t);  // -Y3' = B^2 + E'(X3' - M)
+  fe_neg_compl(r.y, t);
+#else
   fe A, B, C, M, E, t;
   fe_sqr(A, a.x);
   fe_sqr(B, a.y);
@@ -61,6 +85,7 @@ HKV_DEV void gej_double(gej& r, const gej& a) {
   fe_sub(t, M, r.x);
   fe_mul(t, E, t);
   fe_sub(r.y, t, C);        // Y3' = E'(M - X3') - C
+#endif
 }
 
 // Mixed addition r = a + (bx, by) where (bx, by) is affine on the curve whose
@@ -89,10 +114,16 @@ HKV_DEV void gej_add_ge_core(gej& r, const gej& a, const fe& az, const fe& bx, c
   fe_sub(t, t, hhh);
   fe_shl(u2, v, 1);
   fe_sub(t, t, u2);         // X3 = R^2 - H^3 - 2V
+#if HKV_SUM_SCANS
+  fe_sub(v, t, v);
+  fe_mul_sum(v, rr, v, a.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
+  fe_neg_compl(r.y, v);
+#else
   fe_sub(v, v, t);
   fe_mul(v, rr, v);
   fe_mul(hhh, a.y, hhh);
   fe_sub(r.y, v, hhh);      // Y3 = R(V - X3) - Y1 H^3
+#endif
   r.x = t;
 }
 
@@ -129,10 +160,16 @@ HKV_DEV void gej_accumulate(gej& acc, bool& inf, const fe& az, const fe& tx, con
     fe_sub(h, h, hhh);
     fe_shl(t2, hh, 1);
     fe_sub(acc.x, h, t2);     // X3 = R^2 - H^3 - 2V
+#if HKV_SUM_SCANS
+    fe_sub(hh, acc.x, hh);
+    fe_mul_sum(hh, rr, hh, acc.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
+    fe_neg_compl(acc.y, hh);
+#else
     fe_sub(hh, hh, acc.x);
     fe_mul(hh, rr, hh);
     fe_mul(hhh, acc.y, hhh);
     fe_sub(acc.y, hh, hhh);   // Y3 = R(V - X3) - Y1 H^3
+#endif
   }
   const bool degen = live && hz;
   if (__builtin_expect(__any(degen), 0)) {

@@ -56,6 +56,16 @@ enum {
   HKV_DBG_SC_SQR = 35,
   HKV_DBG_SC_IS_HIGH = 36,
   HKV_DBG_INV_MOD_P = 37,      // sgcd::inv_mod_p (a < p; 0 gives 0), out[0..8)
+  // the sum scans and the complement negation: raw | normalised, the row
+  // conventions of ops 22..25
+  HKV_DBG_FE_MUL_SUM = 38,     // a b + next a * next b
+  HKV_DBG_FE_SQRMUL_SUM = 39,  // a^2 + b * next a
+  HKV_DBG_FE_NEG_COMPL = 40,
+  HKV_DBG_FE_MUL_SUM_RA = 41,  // op 38 with the result written over its first operand (r aliases a)
+  HKV_DBG_FE_MUL_SUM_RD = 42,  // op 38 with the result written over its last operand (r aliases d)
+  HKV_DBG_FE_SQRMUL_SUM_RA = 43,  // op 39, r aliases a
+  HKV_DBG_FE_SQRMUL_SUM_RD = 44,  // op 39, r aliases d
+  HKV_DBG_FE_MUL_SUM_RB = 45,  // op 38, r aliases b (the form gej_accumulate and gej_add_ge_core use)
   // Group ops (hkv_debug_group_kernel): lane i takes rows 2i and 2i + 1 (n
   // even, n / 2 lanes). a: k1 | z1, b: k2 | w. The lane's points are
   // P1 = k1 G and P2 = k2 G (ecmult_simple; a zero scalar is infinity), P1

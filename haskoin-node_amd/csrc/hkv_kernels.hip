@@ -2640,6 +2640,32 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
     case HKV_DBG_SC_SQR: sc_sqr(wres, u); for (int k = 0; k < 8; ++k) res[k] = wres.v[k]; break;
     case HKV_DBG_SC_IS_HIGH: res[0] = sc_is_high(u) ? 1u : 0u; break;
     case HKV_DBG_INV_MOD_P: sgcd::inv_mod_p(res, x.v); break;
+    case HKV_DBG_FE_MUL_SUM:
+    case HKV_DBG_FE_MUL_SUM_RA:
+    case HKV_DBG_FE_MUL_SUM_RB:
+    case HKV_DBG_FE_MUL_SUM_RD: {
+      fe xn, yn;
+      load_next(xn, a);
+      load_next(yn, b);
+      if (op == HKV_DBG_FE_MUL_SUM_RA) { fe_mul_sum(x, x, y, xn, yn); z = x; }
+      else if (op == HKV_DBG_FE_MUL_SUM_RB) { fe_mul_sum(y, x, y, xn, yn); z = y; }
+      else if (op == HKV_DBG_FE_MUL_SUM_RD) { fe_mul_sum(yn, x, y, xn, yn); z = yn; }
+      else fe_mul_sum(z, x, y, xn, yn);
+      raw_norm(z);
+      break;
+    }
+    case HKV_DBG_FE_SQRMUL_SUM:
+    case HKV_DBG_FE_SQRMUL_SUM_RA:
+    case HKV_DBG_FE_SQRMUL_SUM_RD: {
+      fe xn;
+      load_next(xn, a);
+      if (op == HKV_DBG_FE_SQRMUL_SUM_RA) { fe_sqrmul_sum(x, x, y, xn); z = x; }
+      else if (op == HKV_DBG_FE_SQRMUL_SUM_RD) { fe_sqrmul_sum(xn, x, y, xn); z = xn; }
+      else fe_sqrmul_sum(z, x, y, xn);
+      raw_norm(z);
+      break;
+    }
+    case HKV_DBG_FE_NEG_COMPL: fe_neg_compl(z, x); raw_norm(z); break;
     default: break;
   }
 #pragma unroll

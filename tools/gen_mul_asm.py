@@ -359,6 +359,85 @@ def reduced_functions():
     return out
 
 
+def reduced_sum_scan(name, sig, cols, preps, doc):
+    """A sum of two 256x256 products, a * b + c * d, given as the concatenated
+    column pair lists of both terms (cols[k] = term 1's column k + term 2's),
+    scanned into one set of accumulators and reduced once, as reduced_scan.
+
+    The operands are weak form (< 2^256), so the sum is < 2^513 and the high
+    half has 257 bits: after column 14 the accumulator's upper word is h[8]
+    (0 or 1), and h[8] * 2^512 == h[8] * (2^32 + 977) * 2^256 enters T.
+    A column takes up to 16 products; its top word counts their carries
+    (<= 16), so init = (top << 32) | h[j-1] < 2^37 and the seeding sums
+    prevhi + init + h[j] * 977 < 2^32 + 2^37 + 2^42 stay below 2^43 as in
+    reduced_scan. T = (L + H * C) >> 256 with L < (2^36 + 15) * 2^256 (the
+    low columns: 2 (k + 1) products of < 2^64 in column k) and H < 2^257,
+    so T < 2^36 + 15 + 2 C + 1 < 2^37, below fe_fold_top's 2^40; the largest T,
+    at all four operands 2^256 - 1, is 2^36 + 2^33 + 1935."""
+    out = [""] + ["// " + l for l in doc] + [
+        f"__device__ __forceinline__ void {name}({sig}) {{",
+        "  uint64_t acc = 0;",
+        "  uint32_t top;",
+        "  uint64_t c0, c1, c2;",
+        "  uint32_t h[9], o[8];",
+        "  const uint32_t k977 = 977u;"]
+    for pr in preps:
+        out += sqr_prep(*pr)
+    for k in range(8, 15):
+        out.append(f"  // column {k}: {len(cols[k])} products")
+        out.append(scan_block(cols[k], "acc"))
+        out.append(f"  h[{k - 8}] = (uint32_t)acc;")
+        out.append("  acc = (acc >> 32) | ((uint64_t)top << 32);")
+    out.append("  const uint64_t h78 = acc;  // h[7] + h[8] * 2^32")
+    out.append("  h[7] = (uint32_t)acc;")
+    out.append("  h[8] = (uint32_t)(acc >> 32);  // the high half of a sum < 2^513 has 257 bits: 0 or 1")
+    for j in range(8):
+        out.append(f"  // column {j}: {len(cols[j])} products + h[{j}] * 977" + (f" + h[{j - 1}]" if j else ""))
+        out.append("  {")
+        out.append("    uint64_t accn;")
+        if j:
+            out.append("    const uint32_t prevhi = (uint32_t)(acc >> 32);")
+            out.append(f"    const uint64_t init = ((uint64_t)top << 32) | h[{j - 1}];")
+            out.append(f"    const uint32_t hj = h[{j}];")
+            blk = scan_block(cols[j], "red")
+        else:
+            blk = scan_block(cols[j], "red0")
+        out.append("  " + blk.replace("\n", "\n  "))
+        out.append("    acc = accn;")
+        out.append("  }")
+        out.append(f"  o[{j}] = (uint32_t)acc;")
+    out.append("  // T < 2^37 (see tools/gen_mul_asm.py reduced_sum_scan): h[8] * 2^512 == h[8] * (2^32 + 977) * 2^256")
+    out.append("  T = ((uint64_t)h[8] * k977 + h78) + (((uint64_t)top << 32) | (acc >> 32));")
+    out.append("  // r may alias any operand: written only after the last column")
+    out.append("#pragma unroll")
+    out.append("  for (int j = 0; j < 8; ++j) r[j] = o[j];")
+    out.append("  (void)c0; (void)c1; (void)c2;")
+    out.append("}")
+    return out
+
+
+def reduced_sum_functions():
+    ab, cd = col_lists("mul", "a", "b"), col_lists("mul", "c", "d")
+    aa = col_lists("sqr", "a", ("ea", "da"))
+    assert max(len(x) + len(y) for x, y in zip(ab, cd)) == 16
+    out = reduced_sum_scan(
+        "mul256_red_sum_ps",
+        "uint32_t r[8], uint64_t& T, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d",
+        [x + y for x, y in zip(ab, cd)], [],
+        ["a * b + c * d mod p in one product scan (HKV_SUM_SCANS): column k sums the",
+         "limb products of both terms into the same accumulators, so the two terms",
+         "share one folded reduction (mul256_red_ps) and one top fold. The high half",
+         "has a ninth limb h[8] (0 or 1), folded into T. Output: r[0..7] and T < 2^37",
+         "with a * b + c * d == r + T * 2^256 (mod p)."])
+    out += reduced_sum_scan(
+        "sqrmul256_red_sum_ps",
+        "uint32_t r[8], uint64_t& T, const uint32_t* a, const uint32_t* c, const uint32_t* d",
+        [x + y for x, y in zip(aa, cd)], [("a", "ea", "da")],
+        ["a^2 + c * d mod p in one product scan: the 43-product square lists of",
+         "sqr256_red_ps and the 64 products of c * d, one folded reduction."])
+    return out
+
+
 def scan_block2(pairs1, pairs2, mode):
     """Two reduced-scan columns (scan_block) interleaved mad by mad, for the
     paired forms. %0 acc1, %1 top1, %2 acc2, %3 top2, %4 %5 carry pairs of
@@ -601,6 +680,7 @@ def main():
     out.extend(row_functions())
     out.extend(reduced_functions())
     out.extend(reduced_pair_functions())
+    out.extend(reduced_sum_functions())
     out.append("")
     out.append("}  // namespace hkv")
     open(OUT, "w").write("\n".join(out) + "\n")
