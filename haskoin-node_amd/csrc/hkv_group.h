@@ -15,12 +15,9 @@ namespace hkv {
 struct ge { fe x, y; };
 struct gej { fe x, y, z; };
 
-// 1: Y3 of gej_double, gej_add_ge_core and gej_accumulate as one sum scan
+// Y3 of gej_double and of the mixed addition (gej_add_tail) is one sum scan
 // (fe_sqrmul_sum / fe_mul_sum: both products reduced once, then negated by
-// complement); 0: two reduced products and a subtraction.
-#ifndef HKV_SUM_SCANS
-#define HKV_SUM_SCANS 1
-#endif
+// complement), not two reduced products and a subtraction.
 
 __constant__ static const uint32_t FE_GX[8] = {0x16F81798u, 0x59F2815Bu, 0x2DCE28D9u, 0x029BFCDBu,
                                                0xCE870B07u, 0x55A06295u, 0xF9DCBBACu, 0x79BE667Eu};
@@ -53,10 +50,9 @@ HKV_DEV void gej_cmov(gej& r, const gej& a, bool f) {
 // (-1.4% ecmult, profiles/r02_variants.log). On this ISA a product costs
 // about a square, so X*B beats the square-and-subtract form. a must not be
 // infinity; y != 0 on secp256k1. r may alias a.
-// With HKV_SUM_SCANS, -Y3' = B^2 + E'(X3' - M) is one sum scan (C is never
-// formed), negated by complement.
+// -Y3' = B^2 + E'(X3' - M) is one sum scan (C is never formed), negated by
+// complement.
 HKV_DEV void gej_double(gej& r, const gej& a) {
-#if HKV_SUM_SCANS
   fe A, B, M, E, t, u;
   fe_sqr(A, a.x);
   fe_sqr(B, a.y);
@@ -70,22 +66,26 @@ HKV_DEV void gej_double(gej& r, const gej& a) {
   fe_sub(t, r.x, M);
   fe_sqrmul_sum(t, B, E, t);  // -Y3' = B^2 + E'(X3' - M)
   fe_neg_compl(r.y, t);
-#else
-  fe A, B, C, M, E, t;
-  fe_sqr(A, a.x);
-  fe_sqr(B, a.y);
-  fe_mul(M, a.x, B);
-  fe_sqr(C, B);
-  fe_mul_small(E, A, 3);
-  fe_half(E, E);            // E' = 3A/2
-  fe_mul(r.z, a.y, a.z);    // Z3' = YZ
-  fe_sqr(t, E);
-  fe_shl(B, M, 1);
-  fe_sub(r.x, t, B);        // X3' = E'^2 - 2M
-  fe_sub(t, M, r.x);
-  fe_mul(t, E, t);
-  fe_sub(r.y, t, C);        // Y3' = E'(M - X3') - C
-#endif
+}
+
+// The tail of the mixed addition, from H = U2 - X1 and R = S2 - Y1 to
+// (X3, Y3, Z3) = a + T (5M + 2S): X3 = R^2 - H^3 - 2V with V = X1 H^2,
+// Z3 = Z1 H, and -Y3 = R(X3 - V) + Y1 H^3 as one sum scan, negated by
+// complement. H != 0. r may alias a: a.x is last read before r.x is written,
+// and a.y is read after r.z and r.x are written, never after r.y.
+HKV_DEV void gej_add_tail(gej& r, const gej& a, const fe& h, const fe& rr) {
+  fe hh, hhh, v, t, t2;
+  fe_sqr(hh, h);
+  fe_mul(hhh, h, hh);       // H^3
+  fe_mul(v, a.x, hh);       // V = X1 H^2
+  fe_mul(r.z, a.z, h);      // Z3 = Z1 H
+  fe_sqr(t, rr);
+  fe_sub(t, t, hhh);
+  fe_shl(t2, v, 1);
+  fe_sub(r.x, t, t2);       // X3 = R^2 - H^3 - 2V
+  fe_sub(v, r.x, v);
+  fe_mul_sum(v, rr, v, a.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
+  fe_neg_compl(r.y, v);
 }
 
 // Mixed addition r = a + (bx, by) where (bx, by) is affine on the curve whose
@@ -96,7 +96,7 @@ HKV_DEV void gej_double(gej& r, const gej& a) {
 // caller must substitute 2a (rz) or infinity (!rz). Writes the z-ratio H.
 HKV_DEV void gej_add_ge_core(gej& r, const gej& a, const fe& az, const fe& bx, const fe& by,
                              bool& hz, bool& rz, fe* zr) {
-  fe z2, u2, s2, h, rr, t, hh, hhh, v;
+  fe z2, u2, s2, h, rr, t;
   fe_sqr(z2, az);
   fe_mul(u2, bx, z2);
   fe_mul(t, az, z2);
@@ -105,26 +105,8 @@ HKV_DEV void gej_add_ge_core(gej& r, const gej& a, const fe& az, const fe& bx, c
   fe_sub(rr, s2, a.y);
   hz = fe_is_zero(h);
   rz = fe_is_zero(rr);
-  fe_sqr(hh, h);
-  fe_mul(hhh, h, hh);
-  fe_mul(v, a.x, hh);
-  fe_mul(r.z, a.z, h);
+  gej_add_tail(r, a, h, rr);
   if (zr) *zr = h;
-  fe_sqr(t, rr);
-  fe_sub(t, t, hhh);
-  fe_shl(u2, v, 1);
-  fe_sub(t, t, u2);         // X3 = R^2 - H^3 - 2V
-#if HKV_SUM_SCANS
-  fe_sub(v, t, v);
-  fe_mul_sum(v, rr, v, a.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
-  fe_neg_compl(r.y, v);
-#else
-  fe_sub(v, v, t);
-  fe_mul(v, rr, v);
-  fe_mul(hhh, a.y, hhh);
-  fe_sub(r.y, v, hhh);      // Y3 = R(V - X3) - Y1 H^3
-#endif
-  r.x = t;
 }
 
 // Complete "accumulate" step used by every ecmult loop:
@@ -150,27 +132,7 @@ HKV_DEV void gej_accumulate(gej& acc, bool& inf, const fe& az, const fe& tx, con
   fe_sub(rr, rr, acc.y);      // R = S2 - Y1
   const bool live = take && !inf;
   const bool hz = fe_is_zero(h);
-  if (live && !hz) {
-    fe hh, hhh, t2;
-    fe_sqr(hh, h);
-    fe_mul(hhh, h, hh);       // H^3
-    fe_mul(hh, acc.x, hh);    // V = X1 H^2
-    fe_mul(acc.z, acc.z, h);  // Z3 = Z1 H
-    fe_sqr(h, rr);
-    fe_sub(h, h, hhh);
-    fe_shl(t2, hh, 1);
-    fe_sub(acc.x, h, t2);     // X3 = R^2 - H^3 - 2V
-#if HKV_SUM_SCANS
-    fe_sub(hh, acc.x, hh);
-    fe_mul_sum(hh, rr, hh, acc.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
-    fe_neg_compl(acc.y, hh);
-#else
-    fe_sub(hh, hh, acc.x);
-    fe_mul(hh, rr, hh);
-    fe_mul(hhh, acc.y, hhh);
-    fe_sub(acc.y, hh, hhh);   // Y3 = R(V - X3) - Y1 H^3
-#endif
-  }
+  if (live && !hz) gej_add_tail(acc, acc, h, rr);
   const bool degen = live && hz;
   if (__builtin_expect(__any(degen), 0)) {
     const bool rz = fe_is_zero(rr);
@@ -263,10 +225,6 @@ HKV_DEV void fe_bc1(fe& r, const fe& a) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) r.v[i] = dpp_bc1(a.v[i]);
 }
-HKV_DEV void fe_bc0(fe& r, const fe& a) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.v[i] = dpp_bc0(a.v[i]);
-}
 // r = a on the even lane, b on the odd lane (odd: all ones on odd lanes)
 HKV_DEV void fe_sel(fe& r, const fe& a, const fe& b, uint32_t odd) {
 #pragma unroll
@@ -304,6 +262,33 @@ HKV_DEV void pair_double(fe& P, fe& Z, uint32_t odd) {
   Z = Q;                      //                | Z3
 }
 
+// The tail of the pair-form mixed addition, from H (even lane), R3 = H^2 | S2
+// and Rr = . | R = S2 - Y1 to (P, Z) = (X3 | Y3, Z3 on the odd lane). H != 0.
+HKV_DEV void pair_add_tail(fe& P, fe& Z, const fe& H, const fe& R3, const fe& Rr, uint32_t odd) {
+  fe O1, O2, R5, R6, W, X3, D, R7, t;
+  fe_sel(O1, H, Rr, odd);     // H              | R
+  fe_sel(O2, R3, Rr, odd);    // H^2            | R
+  fe_mul(R5, O1, O2);         // H^3            | R^2
+  fe_xch(t, H);               //                | H
+  fe_sel(O1, P, Z, odd);      // X1             | Z1
+  fe_sel(O2, R3, t, odd);     // H^2            | H
+  fe_mul(R6, O1, O2);         // V = X1 H^2     | Z3 = Z1 H
+  fe_xch(W, R5);              // R^2            | H^3
+  fe_sub(X3, W, R5);
+  fe_shl(t, R6, 1);
+  fe_sub(X3, X3, t);          // X3 = R^2 - H^3 - 2V
+  fe_sub(D, R6, X3);          // V - X3
+  fe_xch(t, D);               //                | V - X3
+  fe_xch(O1, P);              // Y1             | X1
+  fe_sel(O1, O1, Rr, odd);    // Y1             | R
+  fe_sel(O2, R5, t, odd);     // H^3            | V - X3
+  fe_mul(R7, O1, O2);         // Y1 H^3         | R (V - X3)
+  fe_xch(t, R7);
+  fe_sub(t, R7, t);           //                | Y3 = R (V - X3) - Y1 H^3
+  fe_sel(P, X3, t, odd);
+  Z = R6;                     //                | Z3
+}
+
 // The pair form of gej_accumulate: (P, Z, inf) += T with T = TXY = tx (even
 // lane) | ty (odd lane), affine on the curve of Jacobian scale Z (the
 // accumulator's own isomorphic curve). take must be pair-uniform; lanes at
@@ -321,30 +306,7 @@ HKV_DEV void pair_accumulate(fe& P, fe& Z, bool& inf, const fe& TXY, bool take, 
   fe_sub(Rr, R3, P);          //                | R = S2 - Y1
   const bool live = take && !inf;
   const bool hz = pair_even(fe_is_zero(H));
-  if (live && !hz) {
-    fe R5, R6, W, X3, D, R7, t;
-    fe_sel(O1, H, Rr, odd);   // H              | R
-    fe_sel(O2, R3, Rr, odd);  // H^2            | R
-    fe_mul(R5, O1, O2);       // H^3            | R^2
-    fe_xch(t, H);             //                | H
-    fe_sel(O1, P, Z, odd);    // X1             | Z1
-    fe_sel(O2, R3, t, odd);   // H^2            | H
-    fe_mul(R6, O1, O2);       // V = X1 H^2     | Z3 = Z1 H
-    fe_xch(W, R5);            // R^2            | H^3
-    fe_sub(X3, W, R5);
-    fe_shl(t, R6, 1);
-    fe_sub(X3, X3, t);        // X3 = R^2 - H^3 - 2V
-    fe_sub(D, R6, X3);        // V - X3
-    fe_xch(t, D);             //                | V - X3
-    fe_xch(O1, P);            // Y1             | X1
-    fe_sel(O1, O1, Rr, odd);  // Y1             | R
-    fe_sel(O2, R5, t, odd);   // H^3            | V - X3
-    fe_mul(R7, O1, O2);       // Y1 H^3         | R (V - X3)
-    fe_xch(t, R7);
-    fe_sub(t, R7, t);         //                | Y3 = R (V - X3) - Y1 H^3
-    fe_sel(P, X3, t, odd);
-    Z = R6;                   //                | Z3
-  }
+  if (live && !hz) pair_add_tail(P, Z, H, R3, Rr, odd);
   const bool degen = live && hz;
   if (__builtin_expect(__any(degen), 0)) {
     const bool rz = pair_odd(fe_is_zero(Rr));
@@ -372,85 +334,7 @@ constexpr int QP_0331 = 0x7C;                                   // [0,3,3,1]
 // quad permutation of a product are formed by a single DPP move per limb
 // (P1, P2), and the others by two permutations and one select, not by
 // broadcasts and select chains.
-#ifndef HKV_QUAD_SPLIT  // 1: quad_double's lane-idle products spread over the quad (fe_mul_rows2 / 4)
-#define HKV_QUAD_SPLIT 0
-#endif
-template <int PERM>
-HKV_DEV uint32_t dpp_quad(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, PERM, 0xF, 0xF, false);
-}
-constexpr int QP_X2 = 0x4E, QP_X1 = 0xB1, QP_0101 = 0x44, QP_1 = 0x55;  // [2,3,0,1] [1,0,3,2] [0,1,0,1] [1,1,1,1]
-// Lane-split products: the 64 limb products of one 256 x 256 product spread
-// by rows of a over the lanes of a quad, the partial products summed across
-// lanes by DPP, one reduction. For the products of quad_double that would
-// otherwise leave lanes of the quad idle.
-// r = a b on the lane with hsel = 0 of the pair {q, q ^ 2}; the partner
-// (hsel = all ones) takes a's rows 4..7. Same a, b on both lanes.
-HKV_DEV void fe_mul_rows2(fe& r, const fe& a, const fe& b, uint32_t hsel) {
-  uint32_t ar[4], p[12], t[16];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) ar[k] = (a.v[k] & ~hsel) | (a.v[k + 4] & hsel);
-  mul4x8_ps(p, ar, b.v);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) t[k] = p[k];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) t[4 + k] = addc(p[4 + k], dpp_quad<QP_X2>(p[k]), c);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) t[12 + k] = addc(0u, dpp_quad<QP_X2>(p[8 + k]), c);
-  fe_reduce512(r, t);
-}
-// r = a b on quad lane 1: rows 0,1 of a on lane 1, 2,3 on lane 0, 4,5 on
-// lane 3, 6,7 on lane 2 (m0 / m1 / m2: all ones on quad lane 0 / 1 / 2);
-// the same b on every lane
-HKV_DEV void fe_mul_rows4(fe& r, const fe& a, const fe& b, uint32_t m0, uint32_t m1, uint32_t m2) {
-  const uint32_t m3 = ~(m0 | m1 | m2);
-  uint32_t ar[2], p[10], t1[12], t[16];
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-    ar[k] = (a.v[k] & m1) | (a.v[2 + k] & m0) | (a.v[4 + k] & m3) | (a.v[6 + k] & m2);
-  mul2x8_ps(p, ar, b.v);
-  uint32_t c = 0;
-  t1[0] = p[0];
-  t1[1] = p[1];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) t1[2 + k] = addc(p[2 + k], dpp_quad<QP_X1>(p[k]), c);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) t1[10 + k] = addc(0u, dpp_quad<QP_X1>(p[8 + k]), c);
-  c = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) t[k] = t1[k];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) t[4 + k] = addc(t1[4 + k], dpp_quad<QP_X2>(t1[k]), c);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) t[12 + k] = addc(0u, dpp_quad<QP_X2>(t1[8 + k]), c);
-  fe_reduce512(r, t);
-}
-
 HKV_DEV void quad_double(fe& V, uint32_t m0, uint32_t m1, uint32_t m2) {
-#if HKV_QUAD_SPLIT
-  // [A | B] as two 2-way row-split squares (X^2 on lanes 0, 2; Y^2 on 1, 3),
-  // Y3 = A D - 8C as one 4-way row-split product landing on lane 1
-  fe S, R1, Aq, RA, T, opA, opB, R2, P1, P2, r, t, C8, Dq;
-  fe_quad<QP_0101>(S, V);     // X | Y | X | Y
-  fe_mul_rows2(R1, S, S, ~(m0 | m1));  // A = X^2 | B = Y^2 | . | .
-  fe_quad<QP_0>(Aq, R1);      // A        | A      | A  | A
-  fe_quad<QP_1100>(RA, R1);   // B        | B      | A  | A
-  fe_quad<QP_0112>(T, V);     // X        | .      | Y  | .
-  fe_sel(opA, RA, T, m0 | m2);    // X | B | Y | A
-  fe_sel(opB, RA, V, m2);         // B | B | Z | A
-  fe_mul(R2, opA, opB);       // M | C | YZ | A^2
-  fe_quad<QP_3021>(P1, R2);   // A^2 | M | YZ | C
-  fe_quad<QP_0331>(P2, R2);   // M | A^2 | . | C
-  const uint32_t k1 = m0 ? 9u : (m1 ? 36u : (m2 ? 2u : 0u));
-  const uint32_t k2 = m0 ? 8u : (m1 ? 27u : (m2 ? 0u : 8u));
-  fe_lin2(r, P1, k1, P2, k2); // X3 | D = 36M - 27A^2 | Z3 = 2YZ | -8C
-  fe_quad<QP_3>(C8, r);       // -8C on every lane
-  fe_quad<QP_1>(Dq, r);       // D on every lane
-  fe_mul_rows4(t, Aq, Dq, m0, m1, m2);
-  fe_add(t, t, C8);           // . | Y3 = A D - 8C | . | .
-  fe_sel(V, r, t, m1);        // X3 | Y3 | Z3 | .
-#else
   fe R1, Aq, RA, T, opA, opB, R2, P1, P2, r, t, C8;
   fe_sqr(R1, V);              // A = X^2 | B = Y^2 | . | .
   fe_quad<QP_0>(Aq, R1);      // A        | A      | A  | A
@@ -467,15 +351,14 @@ HKV_DEV void quad_double(fe& V, uint32_t m0, uint32_t m1, uint32_t m2) {
   fe_quad<QP_3>(C8, r);       // -8C on every lane
   fe_mul_add(t, Aq, r, C8);   // . | Y3 = A D - 8C | . | .
   fe_sel(V, r, t, m1);        // X3 | Y3 | Z3 | .
-#endif
 }
 
 // P += TXY in place for a table build: TXY affine on the curve of the
 // accumulator's Jacobian scale, P finite and never +-TXY (the multiples
 // j Q, j < 9, of a point of prime order). Returns the z-ratio H = U2 - X1
-// on the even lane (Z3 = Z1 H). The live branch of pair_accumulate.
+// on the even lane (Z3 = Z1 H). pair_accumulate's sum without its flags.
 HKV_DEV void pair_add_affine(fe& P, fe& Z, const fe& TXY, uint32_t odd, fe& H) {
-  fe z2, O1, O2, R2, R3, Rr, R5, R6, W, X3, D, R7, t;
+  fe z2, O1, O2, R2, R3, Rr;
   fe_sqr(z2, Z);              //                | Z^2
   fe_bc1(O2, z2);             // Z^2            | Z^2
   fe_sel(O1, TXY, Z, odd);    // tx             | Z
@@ -485,27 +368,7 @@ HKV_DEV void pair_add_affine(fe& P, fe& Z, const fe& TXY, uint32_t odd, fe& H) {
   fe_sel(O2, H, R2, odd);     // H              | Z^3
   fe_mul(R3, O1, O2);         // H^2            | S2 = ty Z^3
   fe_sub(Rr, R3, P);          //                | R = S2 - Y1
-  fe_sel(O1, H, Rr, odd);     // H              | R
-  fe_sel(O2, R3, Rr, odd);    // H^2            | R
-  fe_mul(R5, O1, O2);         // H^3            | R^2
-  fe_xch(t, H);               //                | H
-  fe_sel(O1, P, Z, odd);      // X1             | Z1
-  fe_sel(O2, R3, t, odd);     // H^2            | H
-  fe_mul(R6, O1, O2);         // V = X1 H^2     | Z3 = Z1 H
-  fe_xch(W, R5);              // R^2            | H^3
-  fe_sub(X3, W, R5);
-  fe_shl(t, R6, 1);
-  fe_sub(X3, X3, t);          // X3 = R^2 - H^3 - 2V
-  fe_sub(D, R6, X3);          // V - X3
-  fe_xch(t, D);               //                | V - X3
-  fe_xch(O1, P);              // Y1             | X1
-  fe_sel(O1, O1, Rr, odd);    // Y1             | R
-  fe_sel(O2, R5, t, odd);     // H^3            | V - X3
-  fe_mul(R7, O1, O2);         // Y1 H^3         | R (V - X3)
-  fe_xch(t, R7);
-  fe_sub(t, R7, t);           //                | Y3 = R (V - X3) - Y1 H^3
-  fe_sel(P, X3, t, odd);
-  Z = R6;                     //                | Z3
+  pair_add_tail(P, Z, H, R3, Rr, odd);
 }
 
 // acc += b for two Jacobian points of one curve in pair form, exact in

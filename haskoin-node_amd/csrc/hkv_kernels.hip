@@ -59,9 +59,6 @@ __constant__ static const uint32_t PMN[8] = {0x2FC9BAEEu, 0x402DA172u, 0x50B75FC
 // ---------------------------------------------------------------------------
 // 1. prologue
 // ---------------------------------------------------------------------------
-#ifndef HKV_TOP_MERGE  // 1: a chain from the top window takes the top two windows as one digit (pair_chain)
-#define HKV_TOP_MERGE 1
-#endif
 #ifndef HKV_PROLOGUE_WAVES
 #define HKV_PROLOGUE_WAVES 4  // min waves per SIMD the prologue's register allocation targets
 #endif
@@ -114,6 +111,8 @@ HKV_DEV bool pubkey_parse_rec(const uint32_t* w, fe& x, fe& y) {
 // to be a square here; the finish kernels' y_c^2 == w test rejects a
 // non-square (no y_c exists), and their rare paths test it explicitly.
 // Outputs x, w = x^3 + 7 (normalised) and FLAG_YODD / FLAG_COMP.
+// (The head repeats pubkey_parse_rec's on purpose: shared through a helper it
+// compiled to other code — hkv_prologue_kernel 80 -> 82 VGPRs, 6 -> 5 waves.)
 HKV_DEV bool pubkey_parse_rec_w(const uint32_t* w, fe& x, fe& rhs, uint32_t& pflags) {
   const uint32_t pklen = w[24] & 0xFFu;
   const uint32_t prefix = (w[24] >> 8) & 0xFFu;
@@ -416,15 +415,7 @@ HKV_DEV uint32_t late_u1_lane(const uint32_t* __restrict__ recs, uint32_t i, uin
 // caller's validity so far (updated); sinv is s^-1 (of 1 when !ok) for the u1
 // half (sig_lane_g).
 HKV_DEV void sig_lane_q(sc r, sc s, uint32_t mode, uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, bool& ok,
-                        bool& glv_ok, bool& n1, bool& n2, sc& sinv, unsigned long long* sclk = nullptr) {
-#if HKV_SIG_STAMPS == 4  // measurement builds only: s^-1 and the GLV split of workgroup 0's signature wave
-  auto qmark = [&](int slot) {
-    if (sclk != nullptr && (threadIdx.x & 63) == 0) sclk[4 + slot] = wall_clock64();
-  };
-#else
-  auto qmark = [&](int) {};
-  (void)sclk;
-#endif
+                        bool& glv_ok, bool& n1, bool& n2, sc& sinv) {
   ok = ok && u256_lt(r.v, SC_N) && u256_lt(s.v, SC_N);
   const bool high = sc_is_high(s);
   if (mode == HKV_MODE_HASKOIN) {
@@ -438,11 +429,9 @@ HKV_DEV void sig_lane_q(sc r, sc s, uint32_t mode, uint32_t* __restrict__ im, ui
   if (!ok) sc_set_u32(s, 1);
   sc u2;
   sc_inv(sinv, s);
-  qmark(9);  // (HKV_SIG_STAMPS 4: "hi_table" = s^-1 done)
   sc_mul(u2, r, sinv);
   uint32_t k1[5], k2[5];
   glv_ok = glv_split(u2, k1, n1, k2, n2);
-  qmark(2);  // (HKV_SIG_STAMPS 4: "digits" = u2 and the GLV split done)
   const bool use = ok && glv_ok;
   uint32_t S1[5], S2[5];
 #pragma unroll
@@ -546,13 +535,11 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
                                                                                  StdArgs sa) {
   const uint32_t n_lanes = gridDim.x * WG;
   const uint32_t lane = blockIdx.x * WG + threadIdx.x;
-#if HKV_ECMULT_PARK
   // per-lane LDS slots for state the chain does not touch (the table scale
   // Zg, used only after the last window) and the GLV signs the accumulate
   // reads once per term: at 4 waves per SIMD (128 VGPRs) these were spilled
   // to scratch; LDS is idle in this kernel (9 KiB per workgroup)
   __shared__ uint32_t park[9][WG];
-#endif
   // optional clock probe (hkv_profile_clock): shader-clock and constant-rate
   // counters around block 0's work, so bench.py prices the roofline at the
   // clock the launch actually ran at
@@ -611,11 +598,9 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
         qtab_store(qs, n_lanes, lane, (j - 1), 4, h);
       }
       fe_mul(Zg, p2.z, pj.z);  // total scale: phi_Z2 then phi_Zc, Zc = pj.z
-#if HKV_ECMULT_PARK
 #pragma unroll
       for (int k = 0; k < 8; ++k) park[k][threadIdx.x] = Zg.v[k];
       park[8][threadIdx.x] = (neg1 ? 1u : 0u) | (neg2 ? 2u : 0u);
-#endif
       fe beta;
 #pragma unroll
       for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
@@ -658,7 +643,6 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
     bool dbl = false;       // the first window starts from infinity: no doublings
     int x1 = 0, x2 = 0;     // the merged top window's second terms (pair_chain)
     int nterm = 2;          // Q terms of the current window
-#if HKV_TOP_MERGE
     {
       // the top two windows as one digit in [0, 16] per half, taken as
       // min(m, 8) + (m - 8)+ (pair_chain): two additions where every wave
@@ -675,7 +659,6 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
         nterm = 4;
       }
     }
-#endif
 #pragma unroll 1
     for (; win >= 0; --win) {
       const int d1 = (int)(dw & QDIG_MASK) - QBIAS, d2 = (int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS;
@@ -697,11 +680,7 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
         if (t >= 2 && !__any(take)) continue;
         const int mg = dg < 0 ? -dg : dg;
         const int ie = mg ? mg - 1 : 0;
-#if HKV_ECMULT_PARK
         const bool neg = (dg < 0) != (((park[8][threadIdx.x] >> slot) & 1u) != 0);
-#else
-        const bool neg = (dg < 0) != (slot == 0 ? neg1 : neg2);
-#endif
         fe tx, ty;
         qtab_load(qs, n_lanes, lane, ie, (slot == 0 ? 0 : 4), tx);
         qtab_load(qs, n_lanes, lane, ie, 2, ty);
@@ -718,10 +697,8 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
 
     // hand B' = (X, Y, Z acc * Zg) on E_w to the finish kernel
     fe zt;
-#if HKV_ECMULT_PARK
 #pragma unroll
     for (int k = 0; k < 8; ++k) Zg.v[k] = park[k][threadIdx.x];
-#endif
     fe_mul(zt, acc.z, Zg);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -895,7 +872,6 @@ HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t
   auto digit = [&](uint32_t w) { return (int)((w >> dshift) & QDIG_MASK) - QBIAS; };
   uint32_t dw = valid ? im[(size_t)(IM_DIG + w_hi) * n_pad + i] : DIG_ZERO;
   bool dbl = false;  // the first window starts from infinity: no doublings
-#if HKV_TOP_MERGE
   if (w_hi == NWIN - 1 && w_hi > w_lo) {
     // The top two windows as one digit m = 2^QW d_top + d_next. The GLV
     // halves are < 2^128 in practice (the bound the device split asserts is
@@ -925,7 +901,6 @@ HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t
       dw = (w_hi >= w_lo && valid) ? im[(size_t)(IM_DIG + w_hi) * n_pad + i] : DIG_ZERO;
     }
   }
-#endif
 #pragma unroll 1
   for (int win = w_hi; win >= w_lo; --win) {
     const int dg = digit(dw);
@@ -974,15 +949,6 @@ HKV_DEV void xch_read(const uint32_t* __restrict__ xch, int sigs, uint32_t c, ge
   }
   binf = xch[24 * sigs + c] != 0;
 }
-HKV_DEV void xch_write(uint32_t* __restrict__ xch, int sigs, uint32_t c, const gej& b, bool binf) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    xch[k * sigs + c] = b.x.v[k];
-    xch[(8 + k) * sigs + c] = b.y.v[k];
-    xch[(16 + k) * sigs + c] = b.z.v[k];
-  }
-  xch[24 * sigs + c] = binf ? 1u : 0u;
-}
 
 // ---- the roles both small-batch kernels share ----
 // An input's tx bytes and prevout script as the block kernel's LDS copy
@@ -1028,22 +994,13 @@ HKV_DEV void key_point(uint32_t i, uint32_t n, const uint32_t* __restrict__ recs
 template <bool STD>
 HKV_DEV void sig_wave_parse(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint32_t mode, uint32_t* __restrict__ im,
                             const uint32_t* __restrict__ recs, const StdArgs& sa, StdIn& x, sc& m, sc& sinv,
-                            bool& use, uint32_t& flags, TxView v = {nullptr, nullptr},
-                            unsigned long long* sclk = nullptr) {
-#if HKV_SIG_STAMPS == 2 || HKV_SIG_STAMPS == 4
-  auto smark = [&](int slot) {
-    if (sclk != nullptr && (threadIdx.x & 63) == 0) sclk[4 + slot] = wall_clock64();
-  };
-#else
-  auto smark = [&](int) {};
-#endif
+                            bool& use, uint32_t& flags, TxView v = {nullptr, nullptr}) {
   flags = 0;
   use = false;
   if (!on) return;
   bool ok = i < n, glv_ok, n1, n2;
   uint32_t kw[REC_WORDS];
   key_words_of<STD>(i, n, recs, sa, kw, x, v);
-  smark(1);
   sc r, s;
   if constexpr (STD) {
 #pragma unroll
@@ -1057,8 +1014,7 @@ HKV_DEV void sig_wave_parse(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uin
     rec_be256(s.v, w, 64);
     rec_be256(m.v, w, 0);
   }
-  sig_lane_q(r, s, mode, im, n_pad, i, ok, glv_ok, n1, n2, sinv, sclk);
-  smark(8);
+  sig_lane_q(r, s, mode, im, n_pad, i, ok, glv_ok, n1, n2, sinv);
   use = ok && glv_ok;
   fe kx, kwv;
   uint32_t pflags = 0;
@@ -1109,21 +1065,7 @@ template <bool STD, int SPREAD = 0>
 HKV_DEV void sig_wave_gsum(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint32_t* __restrict__ im,
                            const uint32_t* __restrict__ gtab, uint32_t* __restrict__ aux, uint32_t* __restrict__ recs,
                            const StdArgs& sa, uint32_t* shabuf, StdIn& x, sc m, const sc& sinv, bool use,
-                           uint32_t flags, unsigned long long* sclk = nullptr) {
-  // HKV_SIG_STAMPS (measurement builds only): the signature wave's inner
-  // phases of workgroup 0 overwrite three of the block kernel's phase slots;
-  // 1: lo_table = BIP143 per-tx hashes, digits = sighash, key_sqrt = u1;
-  // 2 (sig_wave_parse): lo_table = the input parse, digits = wave 0's key
-  // point, key_sqrt = s^-1, u2 and the digits; 3 (the block kernel's wave 3):
-  // digits = Q1 received, lo_table = Q1's table built
-#if HKV_SIG_STAMPS == 1
-  auto smark = [&](int slot) {
-    if (sclk != nullptr && (threadIdx.x & 63) == 0) sclk[4 + slot] = wall_clock64();
-  };
-#else
-  auto smark = [&](int) {};
-  (void)sclk;
-#endif
+                           uint32_t flags) {
   uint32_t stdok = 0;
   if constexpr (STD) {
     uint32_t* r32 = recs + (size_t)(on && i < n ? i : 0) * REC_WORDS;
@@ -1134,15 +1076,7 @@ HKV_DEV void sig_wave_gsum(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint
     // launch computes per input instead of an index-kernel pass)
     if constexpr (SPREAD > 0)  // every input that may sign with the BIP143 form
       bip143_tx_hashes_spread(sa.txs, x.row, x.ok && (x.segwit || sa.forkid >= 0), r32 + 8, shabuf, SPREAD, x.T);
-    smark(1);
-#if HKV_EXP_SIGWAVE == 1  // measurement build only (wrong verdicts): no script checks / sighash
-    const bool live = false;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) d[k] = 0;
-#else
     const bool live = std_hash(x, sa.txs, sa.forkid, r32, shabuf, d, r32 + 8, SPREAD != 0);
-#endif
-    smark(2);
     if (on) {
       if (i < n) std_write_record(r32, x, live, d);  // the input's verify record (hkv_std_input_kernel's)
       uint32_t w[8];
@@ -1154,21 +1088,9 @@ HKV_DEV void sig_wave_gsum(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint
   }
   if (!on) return;
   sig_lane_g(m, sinv, use, im, n_pad, i);
-  smark(8);
   gej A;
   bool ainf;
-#if HKV_EXP_SIGWAVE == 2  // measurement build only (wrong STD verdicts): no u1 G on standard inputs
-  if constexpr (STD) {
-    fe_set_u32(A.x, 1);
-    fe_set_u32(A.y, 1);
-    fe_set_u32(A.z, 1);
-    ainf = true;
-  } else {
-    gsum_lane(im, n_pad, gtab, i, (flags & FLAG_VALID) != 0, A, ainf);
-  }
-#else
   gsum_lane(im, n_pad, gtab, i, (flags & FLAG_VALID) != 0, A, ainf);
-#endif
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     aux[(size_t)(AUX_AX + k) * n_pad + i] = A.x.v[k];
@@ -1586,12 +1508,6 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
   const uint32_t odd = (ln & 1u) ? 0xFFFFFFFFu : 0u;
   const bool stamp = clk != nullptr && blockIdx.x == 0 && ln == 0;
   auto mark = [&](int slot) {
-#if HKV_SIG_STAMPS
-    if (slot == STAMP_TABLE0 || slot == STAMP_P || slot == STAMP_SQRT) return;  // the signature wave's
-#endif
-#if HKV_SIG_STAMPS == 4
-    if (slot == STAMP_TABLE1) return;
-#endif
     if (stamp) clk[4 + slot] = wall_clock64();
   };
   if (threadIdx.x < BF_COUNT) bflag[threadIdx.x] = 0;
@@ -1614,12 +1530,12 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
       sc sinv, m;
       StdIn x = {};
       sig_wave_parse<STD>(i, on, n, n_pad, mode, im, recs, sa, x, m, sinv, use, flags,
-                          blk_view<STD>(tcache, ln & (BLK_SIGS - 1)), stamp ? clk : nullptr);
+                          blk_view<STD>(tcache, ln & (BLK_SIGS - 1)));
       blk_post(&bflag[BF_SIG], seq);
       mark(STAMP_SIG);
       if constexpr (STD) blk_wait(&bflag[BF_H], seq);  // the BIP143 per-tx hashes (wave 0)
       sig_wave_gsum<STD, (STD ? -1 : BLK_SIGS)>(i, on, n, n_pad, im, gtab, aux, recs, sa, shabuf, x, m, sinv, use,
-                                                flags, stamp ? clk : nullptr);
+                                                flags);
       blk_post(&bflag[BF_A], seq);
       mark(STAMP_GSUM);
       // STD: the multisig scan of the group's inputs (off every critical path)
@@ -1656,9 +1572,6 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
     if (wv == 0) {
       ge q;
       key_point<STD>(i, n, recs, sa, q, blk_view<STD>(tcache, c));
-#if HKV_SIG_STAMPS == 2
-      if (stamp) clk[4 + STAMP_P] = wall_clock64();
-#endif
       fe_sel(P, q.x, q.y, odd);
       fe_set_u32(zb, 1);
       pair_table(P, half, odd, qlds[0], hlds[0], ln, Zg);
@@ -1703,18 +1616,12 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
       blk_post(&bflag[BF_Y], seq);
       mark(STAMP_SQRT);
       blk_wait(&bflag[BF_Q], seq);  // Q1 from wave 1
-#if HKV_SIG_STAMPS == 3
-      if (stamp) clk[4 + STAMP_P] = wall_clock64();
-#endif
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         P.v[k] = qpub[odd ? 1 : 0][k][c];
         zb.v[k] = qpub[2][k][c];
       }
       pair_table(P, half, odd, qlds[2], hlds[2], ln, Zg);
-#if HKV_SIG_STAMPS == 3
-      if (stamp) clk[4 + STAMP_TABLE0] = wall_clock64();
-#endif
     }
     blk_wait(&bflag[BF_SIG], seq);  // the digits, r and flags are in im
     if (wv == 0) mark(STAMP_P);

@@ -162,20 +162,10 @@ HKV_DEV void sc_sub(sc& r, const sc& a, const sc& b) {
 }
 HKV_DEV bool sc_is_high(const sc& a) { return u256_lt(SC_HALF_N, a.v); }
 
-HKV_DEV void sc_sqr_n(sc& r, const sc& a, int n) {
-  sc_sqr(r, a);
-  for (int i = 1; i < n; ++i) sc_sqr(r, r);
-}
-
 // r = a^-1 mod n (0 < a < n; a = 0 gives 0): constant-time safegcd
 // (hkv_safegcd.h), ≈ 10x fewer VALU instructions than the Fermat chain
 // a^(n-2) it replaced (255 squarings + 75 multiplications mod n).
 HKV_DEV void sc_inv(sc& r, const sc& a) { sgcd::inv_mod_n(r.v, a.v); }
-
-HKV_DEV void sc_from_be_words(sc& r, const uint32_t w[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.v[i] = __builtin_bswap32(w[7 - i]);
-}
 
 // GLV split constants (oracle/secp256k1_oracle.py derives the basis).
 // g1 = round(2^384 * b2 / n), g2 = round(2^384 * (-b1) / n)

@@ -17,7 +17,7 @@ def test_radix32_xy_table_saves_under_two_percent():
     """radix-32 windows with an (x, y)-only 16-entry
     table forming beta * x per lambda addition. The doubled per-signature
     table build eats the 14 saved additions; against radix 16 with its top
-    two windows merged (HKV_TOP_MERGE) the (x, y)-only table costs more
+    two windows merged (pair_chain) the (x, y)-only table costs more
     products and the stored-beta one saves 0.5 %, below the 2% adoption bar
     before any memory effect, so neither is built."""
     base = oc.ecmult_products()

@@ -60,7 +60,7 @@ def booth(k, w, nwin):
 
 
 def test_top_window_merge_digit_range():
-    """HKV_TOP_MERGE (pair_chain, hkv_ecmult_kernel): the top two radix-16
+    """The merged top window (pair_chain, hkv_ecmult_kernel): the top two radix-16
     windows of a GLV half run as one digit m = 16 d32 + d31, taken from the
     8-entry table as min(m, 8) + (m - 8)+. That needs m in [0, 16] for every
     half: the rounding split bounds |k1| by (|a1| + |a2|) / 2 and |k2| by
