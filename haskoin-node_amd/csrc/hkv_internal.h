@@ -140,17 +140,6 @@ struct MsTail {
 };
 hipError_t launch_ms_tail(const MsTail& a, uint32_t grid, hipStream_t st);  // grid <= n_cu (its scratch slots)
 uint32_t ms_tail_slots(uint32_t n_cu);  // signatures in flight (im / aux slots the tail needs)
-// small batches of standard inputs in one launch; with ms, the block kernel
-// (std_split_scans) also runs the multisig scan; with tx_off (the block
-// kernel only), it builds the index rows of its inputs' txs into txt itself
-// (no index launch before it)
-hipError_t launch_std_verify_split(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
-                                   uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, uint32_t n_pad,
-                                   int32_t forkid, uint8_t* recs, uint32_t* im, const uint32_t* gtab, uint32_t* qs,
-                                   uint32_t* aux, uint32_t* bits, uint32_t n_words, unsigned long long* clk,
-                                   uint32_t n_cu, const MsScan* ms, const uint32_t* tx_off, hipStream_t st);
-bool std_split_scans(uint32_t n_pad, uint32_t n_cu);
-// y-free full-grid batches: u1 * G, the y0 = num / den reduction and the verdict bitmap
 // the operands of a standard-input batch (txs, index rows, prevout scripts, jobs)
 struct StdOps {
   const uint8_t* txs;
@@ -161,13 +150,23 @@ struct StdOps {
   const hkv_input_job* jobs;
   int32_t forkid;
 };
+// small batches of standard inputs in one launch; with ms, the block kernel
+// (std_split_scans) also runs the multisig scan; with tx_off (the block
+// kernel only), it builds the index rows of its inputs' txs into txt itself
+// (no index launch before it)
+hipError_t launch_std_verify_split(const StdOps& o, uint32_t n, uint32_t n_pad, uint8_t* recs, uint32_t* im,
+                                   const uint32_t* gtab, uint32_t* qs, uint32_t* aux, uint32_t* bits,
+                                   uint32_t n_words, unsigned long long* clk, uint32_t n_cu, const MsScan* ms,
+                                   const uint32_t* tx_off, hipStream_t st);
+bool std_split_scans(uint32_t n_pad, uint32_t n_cu);
 // mid-size standard-input batches (the overlapped path): std_parse, prologue,
 // s^-1 and GLV in one lane per input at the head of the mid-size ecmult
 // kernel's lanes
 hipError_t launch_std_ecmult_mid(const StdOps& o, uint32_t* im, uint32_t n, uint32_t n_pad, uint32_t* qs,
                                  uint32_t grid, unsigned long long* clk, hipStream_t st);
-// (mid: the paired-product instance; late_recs: large standard-input batches,
-// u1 and the validity from the final records first)
+// y-free full-grid batches: u1 * G, the y0 = num / den reduction and the
+// verdict bitmap (mid: the paired-product instance; late_recs: large
+// standard-input batches, u1 and the validity from the final records first)
 hipError_t launch_finish(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* rare_ctr,
                          uint32_t* bits, uint32_t n_words, bool mid, const void* late_recs, hipStream_t st);
 hipError_t launch_gen_pool(uint64_t seed, uint32_t npool, uint32_t* pool, hipStream_t st);
@@ -186,9 +185,7 @@ hipError_t launch_tx_index(const uint8_t* txs, const uint32_t* tx_off, uint32_t 
 hipError_t launch_sighash(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
                           uint32_t scripts_len, const hkv_sighash_job* jobs, uint32_t n, int32_t forkid, uint8_t* out,
                           uint32_t stride, uint8_t* status, hipStream_t st);
-hipError_t launch_std_inputs(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
-                             uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, int32_t forkid,
-                             uint8_t* recs, hipStream_t st);
+hipError_t launch_std_inputs(const StdOps& o, uint32_t n, uint8_t* recs, hipStream_t st);
 // txHash of every tx (txids: n_tx * 32 bytes, 16-aligned; status: n_tx bytes or null)
 hipError_t launch_txids(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, uint8_t* txids, uint8_t* status,
                         hipStream_t st);
@@ -197,9 +194,7 @@ hipError_t launch_txids(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_t
 hipError_t launch_tx_hashes_only(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, uint32_t hashes,
                                  uint32_t* txt, hipStream_t st);
 // multisig inputs: the scan (hkv_sighash.hip section 4; the tail in hkv_kernels.hip)
-hipError_t launch_ms_scan(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
-                          uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, int32_t forkid,
-                          uint32_t* desc, uint64_t* off, uint64_t* counters, hipStream_t st);
+hipError_t launch_ms_scan(const StdOps& o, uint32_t n, const MsScan& ms, hipStream_t st);
 // hkv_headers.hip
 hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_limit, const uint8_t* prev0,
                           uint8_t* hashes, uint8_t* status, hipStream_t st);

@@ -2921,15 +2921,17 @@ hipError_t launch_ecmult(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_
                        StdArgs{});
   return hipGetLastError();
 }
+static StdArgs std_args(const StdOps& o) {
+  return StdArgs{o.txs, o.n_tx, o.txt, o.scripts, o.scripts_len, o.jobs, o.forkid, nullptr, nullptr, nullptr, nullptr};
+}
 // small batches of standard inputs: parse, the Q chains, the script checks,
 // the sighash and the verdict in one launch (hkv_block_kernel<true> or
 // hkv_pair_split_kernel<true>); txt must hold the batch's tx index rows
-hipError_t launch_std_verify_split(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
-                                   uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, uint32_t n_pad,
-                                   int32_t forkid, uint8_t* recs, uint32_t* im, const uint32_t* gtab, uint32_t* qs,
-                                   uint32_t* aux, uint32_t* bits, uint32_t n_words, unsigned long long* clk,
-                                   uint32_t n_cu, const MsScan* ms, const uint32_t* tx_off, hipStream_t st) {
-  StdArgs sa{txs, n_tx, txt, scripts, scripts_len, jobs, forkid, nullptr, nullptr, nullptr, nullptr};
+hipError_t launch_std_verify_split(const StdOps& o, uint32_t n, uint32_t n_pad, uint8_t* recs, uint32_t* im,
+                                   const uint32_t* gtab, uint32_t* qs, uint32_t* aux, uint32_t* bits,
+                                   uint32_t n_words, unsigned long long* clk, uint32_t n_cu, const MsScan* ms,
+                                   const uint32_t* tx_off, hipStream_t st) {
+  StdArgs sa = std_args(o);
   if (ms != nullptr && block_batch(n_pad, n_cu)) {
     sa.ms_desc = ms->desc;
     sa.ms_off = ms->off;
@@ -2955,9 +2957,6 @@ hipError_t launch_gtable(uint32_t* gtab, hipStream_t st) {
   hipLaunchKernelGGL(hkv_gtable_kernel, dim3(ceil_div((size_t)GTAB_TABLES * GTAB_ENTRIES, WG)), dim3(WG), 0, st,
                      gtab);
   return hipGetLastError();
-}
-static StdArgs std_args(const StdOps& o) {
-  return StdArgs{o.txs, o.n_tx, o.txt, o.scripts, o.scripts_len, o.jobs, o.forkid, nullptr, nullptr, nullptr, nullptr};
 }
 hipError_t launch_std_ecmult_mid(const StdOps& o, uint32_t* im, uint32_t n, uint32_t n_pad, uint32_t* qs,
                                  uint32_t grid, unsigned long long* clk, hipStream_t st) {

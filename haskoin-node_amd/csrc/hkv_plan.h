@@ -1,5 +1,6 @@
 // hkv_plan.h — host-side shard planning, bitmap merging and device failover
-// for the multi-device entry points (hkv_api.cpp verify_from_host). Pure C++
+// for the multi-device entry points (hkv_api.cpp verify_from_host), the chunk
+// schedule of a shard and the layout of the one-buffer host forms. Pure C++
 // (no HIP), so tests/host_plan.cpp drives exactly this code under ASan and
 // UBSan on the CPU.
 //
@@ -11,6 +12,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -53,6 +55,41 @@ inline bool merge_shard_words(uint32_t* out, size_t out_words, const uint32_t* w
   if (w) std::memcpy(out + s.lo / 32, words, w * sizeof(uint32_t));
   return true;
 }
+
+// The chunk lengths of one host-batch shard of len records (hkv_api.cpp
+// enqueue_host_shard): the first chunk is grid_lanes / first_div when
+// len >= 2 * grid_lanes, else all of len; then one resident grid, then each
+// chunk twice the one before, at most max_grids grids; a remainder under one
+// grid joins the chunk before it. Every chunk start is a multiple of 32 (the
+// chunk's verdict words land at hbits + start / 32) when host_chunks_ok
+// holds, which it must: a zero first chunk would never end.
+inline bool host_chunks_ok(size_t grid_lanes, size_t first_div) {
+  return first_div > 0 && grid_lanes / first_div > 0 && grid_lanes / first_div % 32 == 0 && grid_lanes % 32 == 0;
+}
+inline std::vector<size_t> host_chunks(size_t len, size_t grid_lanes, size_t first_div, size_t max_grids) {
+  std::vector<size_t> out;
+  size_t next = len >= 2 * grid_lanes ? grid_lanes / first_div : len;
+  for (size_t off = 0, cl = 0; off < len; off += cl) {
+    cl = std::min(next, len - off);
+    if (len - off - cl < grid_lanes) cl = len - off;
+    next = std::min(std::max(2 * next, grid_lanes), max_grids * grid_lanes);
+    out.push_back(cl);
+  }
+  return out;
+}
+
+// Bump layout of a staging buffer carved into parts: add() each part once, in
+// order, with its byte size and alignment (at most the allocation's own); it
+// returns the part's offset, and total is the bytes to
+// allocate. Sizes and offsets come from the one list.
+struct Layout {
+  size_t total = 0;
+  size_t add(size_t bytes, size_t align) {
+    const size_t at = (total + align - 1) / align * align;
+    total = at + bytes;
+    return at;
+  }
+};
 
 // Only a HIP runtime error from the device's own streams, launches or
 // synchronisation (HKV_E_HIP = -4) says the device is bad. Allocation

@@ -450,12 +450,10 @@ hipError_t launch_sighash(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt
                      jobs, n, forkid, out, stride, status);
   return hipGetLastError();
 }
-hipError_t launch_std_inputs(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
-                             uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, int32_t forkid,
-                             uint8_t* recs, hipStream_t st) {
+hipError_t launch_std_inputs(const StdOps& o, uint32_t n, uint8_t* recs, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(hkv_std_input_kernel, dim3((n + xtpb_for(n) - 1) / xtpb_for(n)), dim3(xtpb_for(n)), 0, st, txs, n_tx, txt, scripts,
-                     scripts_len, jobs, n, forkid, recs);
+  hipLaunchKernelGGL(hkv_std_input_kernel, dim3((n + xtpb_for(n) - 1) / xtpb_for(n)), dim3(xtpb_for(n)), 0, st, o.txs,
+                     o.n_tx, o.txt, o.scripts, o.scripts_len, o.jobs, n, o.forkid, recs);
   return hipGetLastError();
 }
 
@@ -466,16 +464,15 @@ hipError_t launch_std_inputs(const uint8_t* txs, uint32_t n_tx, const uint32_t* 
 // ---------------------------------------------------------------------------
 namespace hkv {
 
-// per-input desc words and record offsets; *counters (the call's parity
+// per-input desc words and record offsets; *ms.counters (the call's parity
 // word, zeroed by the call before) ends as the number of candidate records |
 // key-check records << 32 (the tail kernel reads it, stream-ordered after the
 // scan)
-hipError_t launch_ms_scan(const uint8_t* txs, uint32_t n_tx, const uint32_t* txt, const uint8_t* scripts,
-                          uint32_t scripts_len, const hkv_input_job* jobs, uint32_t n, int32_t forkid,
-                          uint32_t* desc, uint64_t* off, uint64_t* counters, hipStream_t st) {
+hipError_t launch_ms_scan(const StdOps& o, uint32_t n, const MsScan& ms, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(hkv_ms_scan_kernel, dim3(blocks_for(n)), dim3(WG), 0, st, txs, n_tx, txt, scripts, scripts_len,
-                     jobs, n, forkid, desc, off, reinterpret_cast<unsigned long long*>(counters));
+  hipLaunchKernelGGL(hkv_ms_scan_kernel, dim3(blocks_for(n)), dim3(WG), 0, st, o.txs, o.n_tx, o.txt, o.scripts,
+                     o.scripts_len, o.jobs, n, o.forkid, ms.desc, ms.off,
+                     reinterpret_cast<unsigned long long*>(ms.counters));
   return hipGetLastError();
 }
 

@@ -2,7 +2,9 @@
 // merge and device failover of hkv_api.cpp verify_from_host), built by
 // tests/test_host_plan.py with -fsanitize=address,undefined: the same header
 // the library compiles, driven by mock devices whose enqueue / join fail on
-// a random schedule. Prints "ok <cases>" or the first failure and exits 1.
+// a random schedule; then the host-batch chunk schedule (host_chunks) and the
+// staging layout (Layout) of the same header. Prints "ok <cases>" or the
+// first failure and exits 1.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -99,9 +101,104 @@ static bool check_failover(std::mt19937_64& rng, size_t n, int nd) {
   return true;
 }
 
+// the chunk schedule as enqueue_host_shard stepped it before host_chunks: an
+// independent transcription, kept here to compare against
+static std::vector<size_t> chunks_by_stepping(size_t len, size_t grid_lanes, size_t first_div, size_t max_grids) {
+  std::vector<size_t> out;
+  const size_t first = len >= 2 * grid_lanes ? grid_lanes / first_div : len;
+  size_t next = first, off = 0;
+  while (off < len) {
+    size_t cl = next < len - off ? next : len - off;
+    if (len - off - cl < grid_lanes) cl = len - off;
+    size_t grown = 2 * next > grid_lanes ? 2 * next : grid_lanes;
+    next = grown < max_grids * grid_lanes ? grown : max_grids * grid_lanes;
+    out.push_back(cl);
+    off += cl;
+  }
+  return out;
+}
+
+static bool check_chunks(size_t len, size_t grid_lanes, size_t first_div, size_t max_grids) {
+  CHECK(hkv::host_chunks_ok(grid_lanes, first_div), "host_chunks_ok(%zu, %zu)", grid_lanes, first_div);
+  const std::vector<size_t> c = hkv::host_chunks(len, grid_lanes, first_div, max_grids);
+  size_t at = 0;
+  for (size_t k = 0; k < c.size(); ++k) {
+    CHECK(at % 32 == 0, "chunk %zu starts at %zu (len=%zu grid=%zu)", k, at, len, grid_lanes);
+    CHECK(c[k] > 0, "empty chunk %zu (len=%zu grid=%zu)", k, len, grid_lanes);
+    CHECK(k == 0 || c[k] >= grid_lanes, "chunk %zu of %zu is under one grid (len=%zu grid=%zu)", k, c[k], len,
+          grid_lanes);
+    CHECK(c[k] <= (max_grids + 1) * grid_lanes, "chunk %zu of %zu is over %zu grids (len=%zu grid=%zu)", k, c[k],
+          max_grids + 1, len, grid_lanes);
+    at += c[k];
+  }
+  CHECK(at == len, "chunks sum to %zu, not %zu (grid=%zu)", at, len, grid_lanes);
+  CHECK(c == chunks_by_stepping(len, grid_lanes, first_div, max_grids), "schedule differs (len=%zu grid=%zu)", len,
+        grid_lanes);
+  return true;
+}
+
+struct Part {
+  size_t bytes, align;
+};
+// lays parts out, checks them, and returns the total through *total
+static bool check_layout(const std::vector<Part>& parts, size_t* total) {
+  hkv::Layout l;
+  size_t end = 0;  // of the part before
+  for (size_t k = 0; k < parts.size(); ++k) {
+    const size_t at = l.add(parts[k].bytes, parts[k].align);
+    CHECK(at >= end, "part %zu at %zu overlaps the one before (ends %zu)", k, at, end);
+    CHECK(at % parts[k].align == 0, "part %zu at %zu is not %zu-aligned", k, at, parts[k].align);
+    CHECK(at - end < parts[k].align, "part %zu at %zu: more padding than its alignment after %zu", k, at, end);
+    end = at + parts[k].bytes;
+    CHECK(l.total >= end, "total %zu does not cover part %zu (ends %zu)", l.total, k, end);
+  }
+  CHECK(l.total == end, "total %zu past the last part's end %zu", l.total, end);
+  *total = l.total;
+  return true;
+}
+
 int main() {
   std::mt19937_64 rng(0x504C414E);
   size_t cases = 0;
+  // the host-batch chunk schedule
+  {
+    const std::vector<size_t> pinned = {65536, 262144, 720896};
+    if (hkv::host_chunks(1048576, 262144, 4, 8) != pinned) {
+      std::printf("FAIL: pinned chunk schedule\n");
+      return 1;
+    }
+    if (hkv::host_chunks(0, 262144, 4, 8).size() != 0 || hkv::host_chunks_ok(0, 4) || hkv::host_chunks_ok(64, 4) ||
+        hkv::host_chunks_ok(3, 4) || hkv::host_chunks_ok(262144, 0) || !hkv::host_chunks_ok(128, 4)) {
+      std::printf("FAIL: host_chunks edge cases\n");
+      return 1;
+    }
+    for (size_t grid_lanes : {128ul, 256ul, 384ul, 1280ul, 65536ul, 262144ul})
+      for (int it = 0; it < 2000; ++it) {
+        // lengths around the schedule's turns (whole grids, the doubling, the cap) and anywhere up to 40 grids
+        const size_t grids = rng() % 40, len = it % 2 ? rng() % (40 * grid_lanes) : grids * grid_lanes + rng() % 3 - 1;
+        if (len > 40 * grid_lanes) continue;  // (0 grids - 1)
+        if (!check_chunks(len, grid_lanes, 4, 8) || !check_chunks(len, grid_lanes, 1, 1 + rng() % 8)) return 1;
+        ++cases;
+      }
+  }
+  // the staging layout
+  {
+    for (size_t n : {1ul, 300ul}) {  // hkv_check_headers: limit | prev | headers | hashes | status
+      size_t total = 0;
+      if (!check_layout({{32, 4}, {32, 4}, {n * 80, 4}, {n * 32, 16}, {n, 1}}, &total)) return 1;
+      if (total > 64 + n * 113 + (4 - 1) * 3 + (16 - 1)) {
+        std::printf("FAIL: header layout of %zu takes %zu bytes\n", n, total);
+        return 1;
+      }
+    }
+    for (int it = 0; it < 2000; ++it) {
+      std::vector<Part> parts(1 + rng() % 8);
+      for (Part& p : parts) p = {(size_t)(rng() % 1000), (size_t)1 << (rng() % 5)};
+      size_t total = 0;
+      if (!check_layout(parts, &total)) return 1;
+      ++cases;
+    }
+  }
   for (int nd = 1; nd <= 9; ++nd)
     for (size_t n : {0ul, 1ul, 31ul, 32ul, 63ul, 64ul, 65ul, 127ul, 128ul, 129ul, 1000ul, 4097ul}) {
       for (size_t lo : {0ul, 64ul, 640ul})

@@ -7,7 +7,11 @@ the batch contiguously with 64-aligned starts; after any failure schedule
 that leaves a device healthy every record is verified exactly once and every
 verdict bit lands in place (nothing written past the bitmap); a round never
 puts two shards on one device; failed devices are reported once and never
-used again; with no healthy device the call fails without partial output."""
+used again; with no healthy device the call fails without partial output.
+The same program checks the host-batch chunk schedule (chunks sum to the
+shard, start on verdict-word boundaries, stay between one and max_grids + 1
+grids, and equal the stepping they replaced) and the staging layout (parts
+aligned, disjoint and covered by the total)."""
 import os
 import subprocess
 
