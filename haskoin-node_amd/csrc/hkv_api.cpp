@@ -1,7 +1,8 @@
 // hkv_api.cpp — the C ABI (include/hkv.h) over the HIP kernels.
 //
 // One hkv_ctx per process; per device: a stream, the fixed-base G tables,
-// the per-lane Q-table scratch sized for one full-occupancy ecmult grid, and
+// the per-lane Q-table scratch sized for one full-occupancy ecmult grid (for
+// a chunk of per-signature tables once a batch is above half that grid), and
 // growable intermediate / bitmap / record-staging buffers. hkv_verify shards
 // contiguous 64-aligned index ranges over the devices, overlaps their H2D /
 // kernels / D2H on per-device streams and joins. No exceptions cross the ABI.
@@ -73,6 +74,10 @@ struct PinnedMem {
 // be in flight: that is safe only because hipFree waits for the whole device
 // first — which is also why a reserve between the chunks of a pipeline is to
 // be avoided (enqueue_host_shard sizes once for its largest chunk).
+// A failed reserve leaves the buffer EMPTY (null, size 0), not at its old
+// size: a buffer that later calls use must be reserved again by those calls
+// before they use it (ensure_dev_buffers does that for im, bits and qs), so
+// that the call after an HKV_E_OOM finds its block again.
 template <class T, class Mem = DeviceMem>
 class DevBuf {
  public:
@@ -91,7 +96,10 @@ class DevBuf {
     if (p_) Mem::release(p_);
     p_ = nullptr, n_ = 0;
     const hipError_t e = Mem::alloc(reinterpret_cast<void**>(&p_), std::max<size_t>(count * sizeof(T), 16));
-    if (e != hipSuccess) return oom_fail(e, what);
+    if (e != hipSuccess) {
+      p_ = nullptr;
+      return oom_fail(e, what);
+    }
     n_ = count;
     return HKV_OK;
   }
@@ -115,7 +123,11 @@ struct DevCtx {
   hipStream_t hash_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   DevBuf<uint32_t> gtab, qs;
-  uint32_t grid_max = 0;  // ecmult blocks (qs is sized for grid_max * WG lanes)
+  uint32_t grid_max = 0;  // ecmult blocks (qs is sized for grid_max * WG lanes at least)
+  // batches above half the resident grid run a table and a chain launch per
+  // chunk of rec_chunk signatures (init_device): qs then holds a table and a
+  // Zg slot per signature of a chunk
+  size_t rec_chunk = 0;
   DevBuf<uint32_t> im;    // IM_WORDS per signature of the largest n_pad
   DevBuf<uint32_t> bits;  // verdict words
   DevBuf<uint8_t> recs;   // host-batch records
@@ -222,8 +234,20 @@ constexpr size_t MS_BAR_WORDS = 32, MS_FAULT = 16, MS_HOST_STATUS = 17;  // DevC
 #endif
 
 int ensure_dev_buffers(DevCtx& d, size_t n_pad) {
-  const int rc = d.im.reserve(n_pad * hkv::IM_WORDS, "hipMalloc(intermediate)");
-  return rc ? rc : d.bits.reserve(n_pad / 32, "hipMalloc(bits)");
+  int rc = d.im.reserve(n_pad * hkv::IM_WORDS, "hipMalloc(intermediate)");
+  if (!rc) rc = d.bits.reserve(n_pad / 32, "hipMalloc(bits)");
+  // the Q tables: one per lane of the resident grid (every launch shape up
+  // to the mid-size one, the multisig tail), and above the mid-size range a
+  // table and a Zg slot per signature of one chunk (800 B each: 839 MB at the
+  // default 2^20, whatever n). Reserved on every call, whatever its size: a
+  // no-op once sized, and after a growth that failed (HKV_E_OOM leaves qs
+  // empty) the next call, of any shape, gets the resident grid's block back.
+  const size_t lanes = (size_t)d.grid_max * hkv::WG;
+  size_t quads = lanes * hkv::QTAB_QUADS;
+  if (n_pad > lanes / 2)
+    quads = std::max(quads, std::min(n_pad, d.rec_chunk) * (hkv::QTAB_QUADS + hkv::QTAB_ZG_QUADS));
+  if (!rc) rc = d.qs.reserve(quads * 4, "hipMalloc(qtab scratch)");
+  return rc;
 }
 
 // Order a call on stream st after the previous user of the device's scratch
@@ -307,7 +331,8 @@ int enqueue_verify(DevCtx& d, const void* d_records, size_t n, uint32_t mode, hi
             "ecmult launch");
   else
     HKV_TRY(hkv::launch_ecmult(d.im, (uint32_t)n, (uint32_t)n_pad, d.gtab, d.qs, blocks, vbits, n_words, split, mid,
-                               d.profile ? d.clk.get() : nullptr, d.aux, d_records, mode, (uint32_t)d.n_cu, st),
+                               d.profile ? d.clk.get() : nullptr, d.aux, d_records, mode, (uint32_t)d.n_cu,
+                               (uint32_t)d.rec_chunk, st),
             "ecmult launch");
   // full-grid batches: the finish kernels add u1 * G and decide x(R) == r
   // through y_c = num / den (hkv_kernels.hip §2b). The rare-lane count is
@@ -378,6 +403,13 @@ int init_device(DevCtx& d, int device) {
   if (const char* e = std::getenv("HKV_STD_CHUNK")) {
     const unsigned long long c = std::strtoull(e, nullptr, 10) / 64 * 64;
     if (c >= 64 && c <= (1ull << 24)) d.std_chunk = (size_t)c;
+  }
+  // the table / chain launches' chunk (test hook: several chunks and a
+  // ragged last one); a multiple of WG, at most the default
+  d.rec_chunk = HKV_REC_CHUNK;
+  if (const char* e = std::getenv("HKV_REC_CHUNK")) {
+    const unsigned long long c = std::strtoull(e, nullptr, 10) / hkv::WG * hkv::WG;
+    if (c >= (unsigned long long)hkv::WG && c <= HKV_REC_CHUNK) d.rec_chunk = (size_t)c;
   }
   const size_t lanes = (size_t)d.grid_max * hkv::WG;
   HKV_RC(d.qs.reserve(lanes * hkv::QTAB_QUADS * 4, "hipMalloc(qtab scratch)"));
@@ -848,6 +880,14 @@ int hkv_debug_ms_window(hkv_ctx* ctx, int dev, uint32_t cand_records, uint32_t k
   DevCtx& d = ctx->devs[(size_t)dev];
   d.ms_win_cand = (uint32_t)round_up(cand_records, 64);
   d.ms_win_keys = (uint32_t)round_up(key_records, 64);
+  return HKV_OK;
+}
+
+int hkv_debug_q_scratch(hkv_ctx* ctx, int dev, size_t* bytes, size_t* chunk) {
+  if (!dev_ok(ctx, dev) || !bytes || !chunk) return HKV_E_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  *bytes = ctx->devs[(size_t)dev].qs.size() * sizeof(uint32_t);
+  *chunk = ctx->devs[(size_t)dev].rec_chunk;
   return HKV_OK;
 }
 

@@ -86,10 +86,12 @@ enum {
 namespace hkv {
 hipError_t launch_prologue(const void* recs, uint32_t n, uint32_t n_pad, uint32_t mode, uint32_t* im,
                            hipStream_t st);
+// chunk: signatures per table / chain launch pair of a batch above the
+// mid-size range (qs holds chunk * (QTAB_QUADS + QTAB_ZG_QUADS) quads then)
 hipError_t launch_ecmult(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* qs,
                          uint32_t grid, uint32_t* bits, uint32_t n_words, bool split, bool mid,
                          unsigned long long* clk, uint32_t* aux, const void* recs, uint32_t mode, uint32_t n_cu,
-                         hipStream_t st);
+                         uint32_t chunk, hipStream_t st);
 hipError_t launch_gtable(uint32_t* gtab, hipStream_t st);
 // the multisig scan operands a fused launch may take over (hkv_ms_scan_kernel's);
 // counters: this call's running sum (candidates | key checks << 32), one of

@@ -7,11 +7,14 @@
 //      w = x^3 + 7 instead of the sqrt), high-S policy, m = msg mod n, s^-1
 //      (batched), u1 = m/s, u2 = r/s, GLV split of u2, Booth digits. Writes a
 //      SoA intermediate.
-//   2. hkv_ecmult_kernel<ILP> — per-lane table of 1..2^(QW-1) * Q' (8
-//      entries at the default radix 16) on an isomorphic curve of E_w (one
+//   2. hkv_ecmult_kernel<true, STDPRO> (mid-size batches) — per-lane table
+//      of 1..2^(QW-1) * Q' (8 entries at the default radix 16) on an isomorphic curve of E_w (one
 //      common Z, so all Q additions are mixed), then a shared doubling chain
 //      of 132 bits with radix-16 Booth digits for k1*Q' and k2*(lambda Q')
-//      (ILP = the paired-form instance for mid-size batches); it leaves
+//      (only the paired-form instance, ILP = true, remains; above the
+//      mid-size range the same two phases run as two launches, 2a:
+//      hkv_qtable_kernel then hkv_chain_kernel, over per-signature tables,
+//      with the plain forms); it leaves
 //      B' = u2*Q' to
 //   2b. hkv_finish_kernel, hkv_rare_kernel, hkv_yverdict_kernel — u1*G from
 //      per-window tables, y0 = num/den from "x(u1 G + u2 Q) == r", and the
@@ -518,21 +521,167 @@ HKV_DEV void gsum_lane(const uint32_t* __restrict__ im, uint32_t n_pad, const ui
                        bool valid, gej& A, bool& ainf);
 HKV_DEV void gej_add_var(gej& acc, bool& inf, const gej& b, bool binf);
 HKV_DEV bool x_matches_r(const fe& Xin, const fe& Z, const uint32_t r[8]);
+
+// the lane's key as Q' = (x w, w^2) on E_w (IM_QY holds w = x^3 + 7)
+HKV_DEV void lane_q(ge& q, const uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, bool valid) {
+  fe x, w;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    x.v[k] = im[(size_t)(IM_QX + k) * n_pad + i];
+    w.v[k] = im[(size_t)(IM_W + k) * n_pad + i];
+  }
+  fe_mul(q.x, x, w);
+  fe_sqr(q.y, w);
+  if (!valid) ge_set_g(q);  // dummy point; all digits are zero for this lane
+}
+
+// The lane's Q table: j*Q', j = 1..QTAB_ENTRIES, affine on the isomorphic
+// curve of scale Zg, with beta*x beside every entry.
+// Pass 1 streams raw entries to the lane's scratch (z-ratios H_j parked in
+// the beta*x slot of entry j-1); pass 2 walks back rescaling every entry
+// to the common Z (rho_j = prod_{k>j} H_k) and writes beta*x.
+HKV_DEV void qtable_build(const ge& q, uint32_t* __restrict__ qs, uint32_t n_lanes, uint32_t lane, fe& Zg) {
+  gej p2, pj;
+  gej_set_ge(p2, q);
+  gej_double(p2, p2);  // 2Q (Jacobian, scale Z2)
+  fe z2, qx, qy;       // Q' = phi_Z2(Q) = (x Z2^2, y Z2^3)
+  fe_sqr(z2, p2.z);
+  fe_mul(qx, q.x, z2);
+  fe_mul(z2, z2, p2.z);
+  fe_mul(qy, q.y, z2);
+  qtab_store(qs, n_lanes, lane, 0, 0, qx);
+  qtab_store(qs, n_lanes, lane, 0, 2, qy);
+  qtab_store(qs, n_lanes, lane, 1, 0, p2.x);
+  qtab_store(qs, n_lanes, lane, 1, 2, p2.y);
+  pj.x = p2.x;
+  pj.y = p2.y;
+  fe_set_u32(pj.z, 1);
+#pragma unroll 1
+  for (int j = 2; j < QTAB_ENTRIES; ++j) {  // P_{j+1} = P_j + Q' (mixed, never degenerate)
+    bool hz, rz;
+    fe h;
+    gej_add_ge_core(pj, pj, pj.z, qx, qy, hz, rz, &h);
+    qtab_store(qs, n_lanes, lane, j, 0, pj.x);
+    qtab_store(qs, n_lanes, lane, j, 2, pj.y);
+    qtab_store(qs, n_lanes, lane, (j - 1), 4, h);
+  }
+  fe_mul(Zg, p2.z, pj.z);  // total scale: phi_Z2 then phi_Zc, Zc = pj.z
+  fe beta;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
+  {
+    fe bx;
+    fe_mul(bx, pj.x, beta);
+    qtab_store(qs, n_lanes, lane, QTAB_ENTRIES - 1, 4, bx);
+  }
+  fe rho;
+  fe_set_u32(rho, 1);
+#pragma unroll 1
+  for (int j = QTAB_ENTRIES - 2; j >= 0; --j) {
+    fe x, y, t;
+    if (j >= 1) {
+      qtab_load(qs, n_lanes, lane, j, 4, t);  // H_{j+1}
+      fe_mul(rho, rho, t);
+    }
+    qtab_load(qs, n_lanes, lane, j, 0, x);
+    qtab_load(qs, n_lanes, lane, j, 2, y);
+    fe_sqr(t, rho);
+    fe_mul(x, x, t);
+    fe_mul(t, t, rho);
+    fe_mul(y, y, t);
+    qtab_store(qs, n_lanes, lane, j, 0, x);
+    qtab_store(qs, n_lanes, lane, j, 2, y);
+    fe_mul(x, x, beta);
+    qtab_store(qs, n_lanes, lane, j, 4, x);
+  }
+}
+
+// The shared doubling chain of k1 * Q' + k2 * lambda(Q'), 33 radix-16 windows
+// from the top, over the lane's table: acc, inf = the sum B' on the table's
+// curve. Window w's digit word is loaded one window ahead, hiding its
+// latency. signs: the lane's GLV signs (bit 0: k1, bit 1: k2), read once per
+// term from the caller's LDS slot.
+template <bool ILP>
+HKV_DEV void q_chain(gej& acc, bool& inf, const uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, bool valid,
+                     const uint32_t* __restrict__ qs, uint32_t n_lanes, uint32_t lane, const uint32_t& signs) {
+  inf = true;
+  fe_set_zero(acc.x);
+  fe_set_zero(acc.y);
+  fe_set_zero(acc.z);
+  uint32_t dw = valid ? im[(size_t)(IM_DIG + NWIN - 1) * n_pad + i] : DIG_ZERO;
+  int win = NWIN - 1;
+  bool dbl = false;       // the first window starts from infinity: no doublings
+  int x1 = 0, x2 = 0;     // the merged top window's second terms (pair_chain)
+  int nterm = 2;          // Q terms of the current window
+  {
+    // the top two windows as one digit in [0, 16] per half, taken as
+    // min(m, 8) + (m - 8)+ (pair_chain): two additions where every wave
+    // ran the second window's 4 doublings (5 % of the halves reach 2^127)
+    const uint32_t dw2 = valid ? im[(size_t)(IM_DIG + NWIN - 2) * n_pad + i] : DIG_ZERO;
+    const int t1 = (((int)(dw & QDIG_MASK) - QBIAS) << QW) + (int)(dw2 & QDIG_MASK) - QBIAS;
+    const int t2 = (((int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS) << QW) + (int)((dw2 >> QDIG_BITS) & QDIG_MASK) - QBIAS;
+    if (!__any(t1 < 0 || t1 > 2 * QBIAS || t2 < 0 || t2 > 2 * QBIAS)) {
+      const int e1 = t1 < QBIAS ? t1 : QBIAS, e2 = t2 < QBIAS ? t2 : QBIAS;
+      x1 = t1 - e1;
+      x2 = t2 - e2;
+      dw = (uint32_t)(e1 + QBIAS) | ((uint32_t)(e2 + QBIAS) << QDIG_BITS);
+      win = NWIN - 2;
+      nterm = 4;
+    }
+  }
+#pragma unroll 1
+  for (; win >= 0; --win) {
+    const int d1 = (int)(dw & QDIG_MASK) - QBIAS, d2 = (int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS;
+    const uint32_t dw_next = (win > 0 && valid) ? im[(size_t)(IM_DIG + win - 1) * n_pad + i] : DIG_ZERO;
+    if (dbl) {
+#pragma unroll 1
+      for (int d = 0; d < QW; ++d) {
+        if (!inf) ec_double<ILP>(acc);
+      }
+    }
+    dbl = true;
+    // Q terms: slot 0 = k1 * Q', slot 1 = k2 * lambda(Q') (terms 2, 3: the
+    // merged top window's second terms, run only when a lane of the wave has one)
+#pragma unroll 1
+    for (int t = 0; t < nterm; ++t) {
+      const int slot = t & 1;
+      const int dg = t < 2 ? (slot == 0 ? d1 : d2) : (slot == 0 ? x1 : x2);
+      const bool take = dg != 0;
+      if (t >= 2 && !__any(take)) continue;
+      const int mg = dg < 0 ? -dg : dg;
+      const int ie = mg ? mg - 1 : 0;
+      const bool neg = (dg < 0) != (((signs >> slot) & 1u) != 0);
+      fe tx, ty;
+      qtab_load(qs, n_lanes, lane, ie, (slot == 0 ? 0 : 4), tx);
+      qtab_load(qs, n_lanes, lane, ie, 2, ty);
+      fe_cneg(ty, ty, neg);
+      const bool was_inf = inf;
+      ec_accumulate<ILP>(acc, inf, acc.z, tx, ty, take);
+      // only the first nonzero digit of a lane starts from infinity: skip
+      // the 24 selects in every window where no lane of the wave does
+      if (__any(take && was_inf)) gej_accumulate_from_inf(acc, inf, tx, ty, take && was_inf);
+    }
+    nterm = 2;
+    dw = dw_next;
+  }
+}
+
 // ILP: the paired-product group forms; full-grid launches of mid-size
 // batches (at most 2 waves per SIMD: 32k-131k signatures) take the <true>
-// instance, which is allocated for 2 waves per SIMD (no spill). The 1M
-// launch keeps the plain forms: its 4 waves per SIMD already fill the issue
-// slots.
+// instance, which is allocated for 2 waves per SIMD (no spill). Larger
+// batches run the table and chain launches (2a below) with the plain forms:
+// their 4 waves per SIMD already fill the issue slots.
 // STDPRO (mid-size standard-input batches): each lane first runs the
 // standard-input lane prologue (1e: std_parse, s^-1, GLV, digits into im)
 // for its input, so the latency-bound prologue phase runs inside this launch's
 // occupancy instead of as a launch of its own before it.
+// (ILP stays a parameter for the instances' names in traces and tools; the
+// plain-form instance went with 2a, so the allocation is the 2-wave one)
 template <bool ILP, bool STDPRO = false>
-__global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_kernel(uint32_t* __restrict__ im,
-                                                                                 uint32_t n, uint32_t n_pad,
-                                                                                 uint32_t* __restrict__ qs,
-                                                                                 unsigned long long* __restrict__ clk,
-                                                                                 StdArgs sa) {
+__global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad,
+                                                           uint32_t* __restrict__ qs,
+                                                           unsigned long long* __restrict__ clk, StdArgs sa) {
+  static_assert(ILP, "only the paired-form (mid-size) instance is built: larger batches run 2a");
   const uint32_t n_lanes = gridDim.x * WG;
   const uint32_t lane = blockIdx.x * WG + threadIdx.x;
   // per-lane LDS slots for state the chain does not touch (the table scale
@@ -554,146 +703,18 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
     const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
     const bool valid = (i < n) && (flags & FLAG_VALID);
     ge q;
-    {
-      fe x, w;  // IM_QY holds w = x^3 + 7: Q' = (x w, w^2) on E_w
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        x.v[k] = im[(size_t)(IM_QX + k) * n_pad + i];
-        w.v[k] = im[(size_t)(IM_W + k) * n_pad + i];
-      }
-      fe_mul(q.x, x, w);
-      fe_sqr(q.y, w);
-      if (!valid) ge_set_g(q);  // dummy point; all digits are zero for this lane
-    }
+    lane_q(q, im, n_pad, i, valid);
     const bool neg1 = (flags & FLAG_NEG1) != 0, neg2 = (flags & FLAG_NEG2) != 0;
 
-    // ---- table: j*Q', j = 1..QTAB_ENTRIES, on the isomorphic curve of scale Zg ----
-    // Pass 1 streams raw entries to the lane's scratch (z-ratios H_j parked in
-    // the beta*x slot of entry j-1); pass 2 walks back rescaling every entry
-    // to the common Z (rho_j = prod_{k>j} H_k) and writes beta*x.
     fe Zg;
-    {
-      gej p2, pj;
-      gej_set_ge(p2, q);
-      gej_double(p2, p2);  // 2Q (Jacobian, scale Z2)
-      fe z2, qx, qy;       // Q' = phi_Z2(Q) = (x Z2^2, y Z2^3)
-      fe_sqr(z2, p2.z);
-      fe_mul(qx, q.x, z2);
-      fe_mul(z2, z2, p2.z);
-      fe_mul(qy, q.y, z2);
-      qtab_store(qs, n_lanes, lane, 0, 0, qx);
-      qtab_store(qs, n_lanes, lane, 0, 2, qy);
-      qtab_store(qs, n_lanes, lane, 1, 0, p2.x);
-      qtab_store(qs, n_lanes, lane, 1, 2, p2.y);
-      pj.x = p2.x;
-      pj.y = p2.y;
-      fe_set_u32(pj.z, 1);
-#pragma unroll 1
-      for (int j = 2; j < QTAB_ENTRIES; ++j) {  // P_{j+1} = P_j + Q' (mixed, never degenerate)
-        bool hz, rz;
-        fe h;
-        gej_add_ge_core(pj, pj, pj.z, qx, qy, hz, rz, &h);
-        qtab_store(qs, n_lanes, lane, j, 0, pj.x);
-        qtab_store(qs, n_lanes, lane, j, 2, pj.y);
-        qtab_store(qs, n_lanes, lane, (j - 1), 4, h);
-      }
-      fe_mul(Zg, p2.z, pj.z);  // total scale: phi_Z2 then phi_Zc, Zc = pj.z
+    qtable_build(q, qs, n_lanes, lane, Zg);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) park[k][threadIdx.x] = Zg.v[k];
-      park[8][threadIdx.x] = (neg1 ? 1u : 0u) | (neg2 ? 2u : 0u);
-      fe beta;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
-      {
-        fe bx;
-        fe_mul(bx, pj.x, beta);
-        qtab_store(qs, n_lanes, lane, QTAB_ENTRIES - 1, 4, bx);
-      }
-      fe rho;
-      fe_set_u32(rho, 1);
-#pragma unroll 1
-      for (int j = QTAB_ENTRIES - 2; j >= 0; --j) {
-        fe x, y, t;
-        if (j >= 1) {
-          qtab_load(qs, n_lanes, lane, j, 4, t);  // H_{j+1}
-          fe_mul(rho, rho, t);
-        }
-        qtab_load(qs, n_lanes, lane, j, 0, x);
-        qtab_load(qs, n_lanes, lane, j, 2, y);
-        fe_sqr(t, rho);
-        fe_mul(x, x, t);
-        fe_mul(t, t, rho);
-        fe_mul(y, y, t);
-        qtab_store(qs, n_lanes, lane, j, 0, x);
-        qtab_store(qs, n_lanes, lane, j, 2, y);
-        fe_mul(x, x, beta);
-        qtab_store(qs, n_lanes, lane, j, 4, x);
-      }
-    }
+    for (int k = 0; k < 8; ++k) park[k][threadIdx.x] = Zg.v[k];
+    park[8][threadIdx.x] = (neg1 ? 1u : 0u) | (neg2 ? 2u : 0u);
 
-    // ---- shared doubling chain, 33 radix-16 windows ----
-    // Window w's digit word is loaded one window ahead, hiding its latency.
     gej acc;
-    bool inf = true;
-    fe_set_zero(acc.x);
-    fe_set_zero(acc.y);
-    fe_set_zero(acc.z);
-    uint32_t dw = valid ? im[(size_t)(IM_DIG + NWIN - 1) * n_pad + i] : DIG_ZERO;
-    int win = NWIN - 1;
-    bool dbl = false;       // the first window starts from infinity: no doublings
-    int x1 = 0, x2 = 0;     // the merged top window's second terms (pair_chain)
-    int nterm = 2;          // Q terms of the current window
-    {
-      // the top two windows as one digit in [0, 16] per half, taken as
-      // min(m, 8) + (m - 8)+ (pair_chain): two additions where every wave
-      // ran the second window's 4 doublings (5 % of the halves reach 2^127)
-      const uint32_t dw2 = valid ? im[(size_t)(IM_DIG + NWIN - 2) * n_pad + i] : DIG_ZERO;
-      const int t1 = (((int)(dw & QDIG_MASK) - QBIAS) << QW) + (int)(dw2 & QDIG_MASK) - QBIAS;
-      const int t2 = (((int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS) << QW) + (int)((dw2 >> QDIG_BITS) & QDIG_MASK) - QBIAS;
-      if (!__any(t1 < 0 || t1 > 2 * QBIAS || t2 < 0 || t2 > 2 * QBIAS)) {
-        const int e1 = t1 < QBIAS ? t1 : QBIAS, e2 = t2 < QBIAS ? t2 : QBIAS;
-        x1 = t1 - e1;
-        x2 = t2 - e2;
-        dw = (uint32_t)(e1 + QBIAS) | ((uint32_t)(e2 + QBIAS) << QDIG_BITS);
-        win = NWIN - 2;
-        nterm = 4;
-      }
-    }
-#pragma unroll 1
-    for (; win >= 0; --win) {
-      const int d1 = (int)(dw & QDIG_MASK) - QBIAS, d2 = (int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS;
-      const uint32_t dw_next = (win > 0 && valid) ? im[(size_t)(IM_DIG + win - 1) * n_pad + i] : DIG_ZERO;
-      if (dbl) {
-#pragma unroll 1
-        for (int d = 0; d < QW; ++d) {
-          if (!inf) ec_double<ILP>(acc);
-        }
-      }
-      dbl = true;
-      // Q terms: slot 0 = k1 * Q', slot 1 = k2 * lambda(Q') (terms 2, 3: the
-      // merged top window's second terms, run only when a lane of the wave has one)
-#pragma unroll 1
-      for (int t = 0; t < nterm; ++t) {
-        const int slot = t & 1;
-        const int dg = t < 2 ? (slot == 0 ? d1 : d2) : (slot == 0 ? x1 : x2);
-        const bool take = dg != 0;
-        if (t >= 2 && !__any(take)) continue;
-        const int mg = dg < 0 ? -dg : dg;
-        const int ie = mg ? mg - 1 : 0;
-        const bool neg = (dg < 0) != (((park[8][threadIdx.x] >> slot) & 1u) != 0);
-        fe tx, ty;
-        qtab_load(qs, n_lanes, lane, ie, (slot == 0 ? 0 : 4), tx);
-        qtab_load(qs, n_lanes, lane, ie, 2, ty);
-        fe_cneg(ty, ty, neg);
-        const bool was_inf = inf;
-        ec_accumulate<ILP>(acc, inf, acc.z, tx, ty, take);
-        // only the first nonzero digit of a lane starts from infinity: skip
-        // the 24 selects in every window where no lane of the wave does
-        if (__any(take && was_inf)) gej_accumulate_from_inf(acc, inf, tx, ty, take && was_inf);
-      }
-      nterm = 2;
-      dw = dw_next;
-    }
+    bool inf;
+    q_chain<ILP>(acc, inf, im, n_pad, i, valid, qs, n_lanes, lane, park[8][threadIdx.x]);
 
     // hand B' = (X, Y, Z acc * Zg) on E_w to the finish kernel
     fe zt;
@@ -708,6 +729,84 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_ECMULT_WAVES) hkv_ecmult_ker
     }
     im[(size_t)IM_FLAGS * n_pad + i] = flags | (inf ? FLAG_BINF : 0u);
   }
+  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+    clk[2] = clock64();
+    clk[3] = wall_clock64();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// 2a. Batches above half the resident grid (the 1M headline, large
+//     standard-input batches): the table build and the window chain as two
+//     launches, one signature per lane at 4 waves per SIMD, over chunks of cn
+//     signatures (i0 .. i0 + cn, cn a multiple of WG). Signature s of the
+//     chunk owns table slot s of qs and the Zg slot behind the chunk's tables
+//     (hkv_layout.h HKV_REC_CHUNK). The table launch is bound by memory (it
+//     streams 2.4 KB per signature), the chain launch by VALU issue. A 1M
+//     chunk is four times the resident grid, so a workgroup slot that frees
+//     early takes the next workgroup. The earlier form, one kernel whose
+//     resident lanes each looped over four signatures, ran the same
+//     instruction count 4.6 % longer at a lower average occupancy, and so do
+//     these launches in chunks of one resident grid:
+//     keep the chunk well above the resident grid.
+// ---------------------------------------------------------------------------
+HKV_DEV uint4* zg_ptr(uint32_t* qs, uint32_t cn, uint32_t s) {
+  return reinterpret_cast<uint4*>(qs) + (size_t)cn * QTAB_QUADS + (size_t)s * QTAB_ZG_QUADS;
+}
+
+__global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_qtable_kernel(const uint32_t* __restrict__ im, uint32_t n,
+                                                                       uint32_t n_pad, uint32_t i0, uint32_t cn,
+                                                                       uint32_t* __restrict__ qs) {
+  const uint32_t s = blockIdx.x * WG + threadIdx.x;  // < cn: the grid is cn / WG blocks
+  const uint32_t i = i0 + s;
+  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  const bool valid = (i < n) && (flags & FLAG_VALID);
+  ge q;
+  lane_q(q, im, n_pad, i, valid);
+  fe Zg;
+  qtable_build(q, qs, cn, s, Zg);
+  uint4* z = zg_ptr(qs, cn, s);
+  z[0] = make_uint4(Zg.v[0], Zg.v[1], Zg.v[2], Zg.v[3]);
+  z[1] = make_uint4(Zg.v[4], Zg.v[5], Zg.v[6], Zg.v[7]);
+}
+
+__global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_chain_kernel(uint32_t* __restrict__ im, uint32_t n,
+                                                                      uint32_t n_pad, uint32_t i0, uint32_t cn,
+                                                                      const uint32_t* __restrict__ qs,
+                                                                      unsigned long long* __restrict__ clk) {
+  // the lane's GLV signs, read once per term (q_chain): held in a register
+  // they were spilled to scratch at 128 VGPRs; LDS is idle in this kernel
+  __shared__ uint32_t signs[WG];
+  // optional clock probe (hkv_profile_clock), as in hkv_ecmult_kernel
+  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+    clk[0] = clock64();
+    clk[1] = wall_clock64();
+  }
+  const uint32_t s = blockIdx.x * WG + threadIdx.x;  // < cn: the grid is cn / WG blocks
+  const uint32_t i = i0 + s;
+  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  const bool valid = (i < n) && (flags & FLAG_VALID);
+  signs[threadIdx.x] = ((flags & FLAG_NEG1) ? 1u : 0u) | ((flags & FLAG_NEG2) ? 2u : 0u);
+  gej acc;
+  bool inf;
+  q_chain<false>(acc, inf, im, n_pad, i, valid, qs, cn, s, signs[threadIdx.x]);
+
+  // hand B' = (X, Y, Z acc * Zg) on E_w to the finish kernel
+  fe Zg, zt;
+  {
+    const uint4* z = zg_ptr(const_cast<uint32_t*>(qs), cn, s);
+    const uint4 v0 = z[0], v1 = z[1];
+    Zg.v[0] = v0.x; Zg.v[1] = v0.y; Zg.v[2] = v0.z; Zg.v[3] = v0.w;
+    Zg.v[4] = v1.x; Zg.v[5] = v1.y; Zg.v[6] = v1.z; Zg.v[7] = v1.w;
+  }
+  fe_mul(zt, acc.z, Zg);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    im[(size_t)(IM_BX + k) * n_pad + i] = acc.x.v[k];
+    im[(size_t)(IM_BX + 8 + k) * n_pad + i] = acc.y.v[k];
+    im[(size_t)(IM_BX + 16 + k) * n_pad + i] = zt.v[k];
+  }
+  im[(size_t)IM_FLAGS * n_pad + i] = flags | (inf ? FLAG_BINF : 0u);
   if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
     clk[2] = clock64();
     clk[3] = wall_clock64();
@@ -2902,10 +3001,28 @@ hipError_t launch_prologue(const void* recs, uint32_t n, uint32_t n_pad, uint32_
 // waves per SIMD, the paired-form instance at a 2-wave register allocation
 static inline bool block_batch(uint32_t n_pad, uint32_t n_cu) { return n_pad <= (uint32_t)BLK_SIGS * n_cu; }
 bool std_split_scans(uint32_t n_pad, uint32_t n_cu) { return block_batch(n_pad, n_cu); }
+// full-grid batches above the mid-size range (2a): the table and chain
+// launches over chunks of at most `chunk` signatures (a multiple of WG; qs
+// holds chunk tables and Zg slots)
+static hipError_t launch_table_chain(uint32_t* im, uint32_t n, uint32_t n_pad, uint32_t* qs, uint32_t chunk,
+                                     unsigned long long* clk, hipStream_t st) {
+  if (chunk < (uint32_t)WG || chunk % WG != 0) return hipErrorInvalidValue;
+  for (uint64_t next = 0; next < n_pad; next += chunk) {  // (64-bit: n_pad may be within a chunk of 2^32)
+    const uint32_t i0 = (uint32_t)next, cn = n_pad - i0 < chunk ? n_pad - i0 : chunk;
+    hipLaunchKernelGGL(hkv_qtable_kernel, dim3(cn / WG), dim3(WG), 0, st, (const uint32_t*)im, n, n_pad, i0, cn, qs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hkv_chain_kernel, dim3(cn / WG), dim3(WG), 0, st, im, n, n_pad, i0, cn, (const uint32_t*)qs,
+                       i0 == 0 ? clk : nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 hipError_t launch_ecmult(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* qs,
                          uint32_t grid, uint32_t* bits, uint32_t n_words, bool split, bool mid,
                          unsigned long long* clk, uint32_t* aux, const void* recs, uint32_t mode, uint32_t n_cu,
-                         hipStream_t st) {
+                         uint32_t chunk, hipStream_t st) {
   uint32_t* rw = const_cast<uint32_t*>((const uint32_t*)recs);
   if (split && block_batch(n_pad, n_cu))
     hipLaunchKernelGGL(hkv_block_kernel<false>, dim3(n_pad / BLK_SIGS), dim3(BLK_TPB), 0, st, im, n, n_pad, gtab, qs,
@@ -2917,8 +3034,7 @@ hipError_t launch_ecmult(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_
     hipLaunchKernelGGL((hkv_ecmult_kernel<true, false>), dim3(grid), dim3(WG), 0, st, im, n, n_pad, qs, clk,
                        StdArgs{});
   else
-    hipLaunchKernelGGL((hkv_ecmult_kernel<false, false>), dim3(grid), dim3(WG), 0, st, im, n, n_pad, qs, clk,
-                       StdArgs{});
+    return launch_table_chain(im, n, n_pad, qs, chunk, clk, st);
   return hipGetLastError();
 }
 static StdArgs std_args(const StdOps& o) {
@@ -3023,8 +3139,16 @@ hipError_t launch_gen_sign(uint64_t seed, uint32_t n, const uint8_t* priv, const
                      msg_stride, sig);
   return hipGetLastError();
 }
+// The resident grid (grid_max = blocks per CU x CUs, hkv_api.cpp) sets the
+// split and mid-size thresholds and the mid-size kernel's grid (half of it).
+// It is defined by the 4-wave allocation of the full-grid chain, 128 VGPRs:
+// HKV_ECMULT_WAVES blocks of 4 waves per CU. The query only confirms that
+// the chain kernel reaches it; a chain kernel that could hold more (fewer
+// registers) must not move the thresholds, so the answer is capped.
 hipError_t ecmult_max_blocks_per_cu(int* out) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, hkv_ecmult_kernel<false>, WG, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(out, hkv_chain_kernel, WG, 0);
+  if (e == hipSuccess && *out > HKV_ECMULT_WAVES) *out = HKV_ECMULT_WAVES;
+  return e;
 }
 
 }  // namespace hkv

@@ -110,6 +110,16 @@ constexpr int QTAB_ENTRIES = QBIAS;
 constexpr int QTAB_QUADS_PER_ENTRY = 6;
 constexpr int QTAB_QUADS = QTAB_ENTRIES * QTAB_QUADS_PER_ENTRY;
 
+// Record batches above half the resident grid (hkv_kernels.hip 2a) build the
+// tables in one launch and run the chains in the next, over chunks of at most
+// this many signatures. Each signature of a chunk of cn owns table slot s
+// (n_lanes = cn) and, behind the chunk's tables, 2 quads for its table scale
+// Zg at quad cn * QTAB_QUADS + 2 s: 800 B per signature, 839 MB at 2^20.
+#ifndef HKV_REC_CHUNK
+#define HKV_REC_CHUNK (1u << 20)
+#endif
+constexpr int QTAB_ZG_QUADS = 2;
+
 constexpr int WG = 256;                // threads per workgroup (4 waves)
 
 // Per-transaction index (hkv_sighash.hip, tx index kernel), AoS rows of

@@ -137,6 +137,12 @@ int hkv_debug_fail_device(hkv_ctx* ctx, int dev, uint32_t when);
  * _scratch reports the bytes the windows hold allocated on device dev. */
 int hkv_debug_ms_window(hkv_ctx* ctx, int dev, uint32_t cand_records, uint32_t key_records);
 int hkv_debug_ms_scratch(hkv_ctx* ctx, int dev, size_t* bytes);
+/* Read-only test hook: the bytes of Q-table scratch device dev holds (one
+ * table per lane of the resident grid from hkv_open on; it grows once to 800 B
+ * per signature of a chunk with the first batch above half that grid) and the
+ * chunk, in signatures, in which such batches run (2^20; HKV_REC_CHUNK, read
+ * at hkv_open, sets a smaller multiple of 256: a test hook). */
+int hkv_debug_q_scratch(hkv_ctx* ctx, int dev, size_t* bytes, size_t* chunk);
 /* Read-only test hook: what device dev's last multisig tail launch saw and
  * did, read after every call enqueued so far has completed. out[0] = the
  * scan's total it ran on (candidate records | key-check records << 32),

@@ -26,7 +26,7 @@ import json
 import re
 import sys
 
-DEFAULT_KERNEL = "_ZN3hkv17hkv_ecmult_kernelILb0ELb0EEEvPjjjS1_PyNS_7StdArgsE"
+DEFAULT_KERNEL = "_ZN3hkv16hkv_chain_kernelEPjjjjjPKjPy"  # the 1M launch's window chain (hkv_kernels.hip 2a)
 
 
 def classify(op: str) -> str:
