@@ -32,8 +32,14 @@
  * checks every golden KAT, the special pool and generated adversarial batches
  * against hkv_oracle.c in both modes; bench.py compares its verdicts with the
  * GPU's on every timed sample.
+ *
+ * At its end: builders of valid records with exact scalars u1 = m / s and
+ * u2 = r / s (hkvo_fast_chosen_records, hkvo_fast_gtable_records), the input
+ * of tests/test_gpu_chosen_scalars.py.
  */
+#define _GNU_SOURCE /* sched_getaffinity: the record builders size their thread pool by it */
 #include <pthread.h>
+#include <sched.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -934,4 +940,306 @@ void hkvo_fast_glv_split(const uint8_t k[32], uint64_t m1[3], int* s1, uint64_t 
   sc x;
   u256_from_be(x.d, k);
   glv_split(&x, m1, s1, m2, s2);
+}
+
+/* ------------------------------------------------------------------------ */
+/* Record builders with exact scalars (tests/test_gpu_chosen_scalars.py): valid
+ * 168-byte records whose verify computes a requested u1 = m / s and/or
+ * u2 = r / s. Record: key Q = d G, R = (u1 + u2 d) G, r = R.x mod n,
+ * s = r / u2, msg32 = u1 s. A verifier only sees the requested scalars when s
+ * is low (a high s is rejected in mode 0 and replaced by n - s in mode 1,
+ * which negates both scalars), so a high s is dealt with per record:
+ *   HKVO_PIN_U1    s <- n - s and Q <- -Q: u1 stays, u2 and Q change sign
+ *                  together (R does not move)
+ *   HKVO_PIN_U2    u1 is free: it is redrawn from a seeded counter until s is low
+ *   HKVO_PIN_BOTH  d is redrawn
+ * with at most HKVO_MAX_REDRAWS redraws. Nothing is skipped silently: u2 = 0,
+ * d = 0, r = 0, R at infinity, a scalar >= n and exhausted redraws are error
+ * returns. */
+#define HKVO_PIN_U1 1
+#define HKVO_PIN_U2 2
+#define HKVO_PIN_BOTH 3
+#define HKVO_MAX_REDRAWS 64
+#define HKVO_E_ARG 1      /* a scalar >= n, d = 0, an unknown pin, a bad table / range */
+#define HKVO_E_U2_ZERO 2
+#define HKVO_E_R_ZERO 3
+#define HKVO_E_INFINITY 4
+#define HKVO_E_REDRAWS 5
+
+static void be_from_u256(uint8_t* b, const uint64_t* v) {
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 8; ++j) b[(3 - i) * 8 + j] = (uint8_t)(v[i] >> (56 - 8 * j));
+}
+static void fe_to_u256(uint64_t v[4], const fe* a) { /* a normalized */
+  v[0] = a->n[0] | a->n[1] << 52;
+  v[1] = a->n[1] >> 12 | a->n[2] << 40;
+  v[2] = a->n[2] >> 24 | a->n[3] << 28;
+  v[3] = a->n[3] >> 36 | a->n[4] << 16;
+}
+/* k G (k < n) from the w = 15 tables, Jacobian on E */
+static void ecmult_gen(gej* r, const sc* k) {
+  const uint64_t g1[3] = {k->d[0], k->d[1], 0}, g2[3] = {k->d[2], k->d[3], 0};
+  int w1[WNAF_LEN], w2[WNAF_LEN];
+  const int l1 = wnaf_var(w1, WNAF_LEN, g1, WINDOW_G, 1);
+  const int l2 = wnaf_var(w2, WNAF_LEN, g2, WINDOW_G, 1);
+  r->inf = 1;
+  for (int i = (l1 > l2 ? l1 : l2) - 1; i >= 0; --i) {
+    gej_double(r, r);
+    int d;
+    ge t;
+    if (i < l1 && (d = w1[i]) != 0) {
+      t = g_pre[(d > 0 ? d : -d) >> 1];
+      if (d < 0) fe_negate(&t.y, &t.y, 1);
+      gej_add_ge(r, r, &t, NULL, NULL);
+    }
+    if (i < l2 && (d = w2[i]) != 0) {
+      t = g_pre128[(d > 0 ? d : -d) >> 1];
+      if (d < 0) fe_negate(&t.y, &t.y, 1);
+      gej_add_ge(r, r, &t, NULL, NULL);
+    }
+  }
+}
+/* finite a -> affine, normalized */
+static void ge_from_gej(ge* r, const gej* a) {
+  fe zi, zi2, zi3;
+  fe_inv(&zi, &a->z);
+  fe_sqr(&zi2, &zi);
+  fe_mul(&zi3, &zi2, &zi);
+  fe_mul(&r->x, &a->x, &zi2);
+  fe_mul(&r->y, &a->y, &zi3);
+  fe_normalize(&r->x);
+  fe_normalize(&r->y);
+}
+/* r = x mod n for a normalized x (< p < 2n) */
+static void sc_from_fe_x(sc* r, const fe* x) {
+  fe_to_u256(r->d, x);
+  if (!u256_lt(r->d, SN)) u256_sub(r->d, r->d, SN);
+}
+/* a scalar in [1, n) from a counter (splitmix64) */
+static void sc_filler(sc* r, uint64_t stream, uint64_t i, uint64_t draw) {
+  uint64_t x = stream * 0xD1342543DE82EF95ULL + i * 0x9E3779B97F4A7C15ULL + draw * 0xBF58476D1CE4E5B9ULL;
+  for (int l = 0; l < 4; ++l) {
+    x += 0x9E3779B97F4A7C15ULL;
+    uint64_t z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    r->d[l] = z ^ (z >> 31);
+  }
+  if (!u256_lt(r->d, SN)) u256_sub(r->d, r->d, SN);
+  if (sc_is_zero(r)) r->d[0] = 1;
+}
+/* msg32 | r | s | pklen | key: compressed (02/03 x) or uncompressed (04 x y);
+ * q normalized; neg: the key -q */
+static void write_record(uint8_t* out, const sc* msg, const sc* r, const sc* s, const ge* q, int neg, int compressed) {
+  memset(out, 0, 168);
+  be_from_u256(out, msg->d);
+  be_from_u256(out + 32, r->d);
+  be_from_u256(out + 64, s->d);
+  fe y = q->y;
+  if (neg) {
+    fe_negate(&y, &y, 1);
+    fe_normalize(&y);
+  }
+  uint64_t xv[4], yv[4];
+  fe_to_u256(xv, &q->x);
+  fe_to_u256(yv, &y);
+  if (compressed) {
+    out[96] = 33;
+    out[97] = (uint8_t)(2 | (yv[0] & 1));
+    be_from_u256(out + 98, xv);
+  } else {
+    out[96] = 65;
+    out[97] = 4;
+    be_from_u256(out + 98, xv);
+    be_from_u256(out + 130, yv);
+  }
+}
+
+/* n records from big-endian 32-byte scalars u1[i], u2[i], d[i] (each < n) and
+ * pin[i] (HKVO_PIN_*); record i has a compressed key when i is even. Returns 0,
+ * or -(8 i + HKVO_E_*) for the first record i that cannot be built. */
+long long hkvo_fast_chosen_records(const uint8_t* u1s, const uint8_t* u2s, const uint8_t* ds, const uint8_t* pin,
+                                   size_t n, uint8_t* out) {
+  pthread_once(&g_once, init_tables);
+  for (size_t i = 0; i < n; ++i) {
+    const long long fail = -(long long)(8 * i);
+    sc u1, u2, d, u2inv, k, r, s, msg;
+    u256_from_be(u1.d, u1s + 32 * i);
+    u256_from_be(u2.d, u2s + 32 * i);
+    u256_from_be(d.d, ds + 32 * i);
+    if (!u256_lt(u1.d, SN) || !u256_lt(u2.d, SN) || !u256_lt(d.d, SN) || sc_is_zero(&d)) return fail - HKVO_E_ARG;
+    if (pin[i] != HKVO_PIN_U1 && pin[i] != HKVO_PIN_U2 && pin[i] != HKVO_PIN_BOTH) return fail - HKVO_E_ARG;
+    if (sc_is_zero(&u2)) return fail - HKVO_E_U2_ZERO;
+    sc_inverse(&u2inv, &u2);
+    int neg = 0;
+    for (int draw = 0;; ++draw) {
+      gej R;
+      ge Ra;
+      sc_mul(&k, &u2, &d);
+      sc_add(&k, &k, &u1);
+      if (sc_is_zero(&k)) return fail - HKVO_E_INFINITY;
+      ecmult_gen(&R, &k);
+      if (R.inf) return fail - HKVO_E_INFINITY;
+      ge_from_gej(&Ra, &R);
+      sc_from_fe_x(&r, &Ra.x);
+      if (sc_is_zero(&r)) return fail - HKVO_E_R_ZERO;
+      sc_mul(&s, &r, &u2inv);
+      if (!sc_is_high(&s)) break;
+      if (pin[i] == HKVO_PIN_U1) {
+        sc_negate(&s, &s);
+        neg = 1;
+        break;
+      }
+      if (draw == HKVO_MAX_REDRAWS) return fail - HKVO_E_REDRAWS;
+      if (pin[i] == HKVO_PIN_U2) sc_filler(&u1, 1, i, (uint64_t)draw);
+      else sc_filler(&d, 2, i, (uint64_t)draw);
+    }
+    gej Q;
+    ge Qa;
+    ecmult_gen(&Q, &d);
+    ge_from_gej(&Qa, &Q);
+    sc_mul(&msg, &u1, &s);
+    write_record(out + 168 * i, &msg, &r, &s, &Qa, neg, (i & 1) == 0);
+  }
+  return 0;
+}
+
+/* j 2^off as a scalar; 0 when it is >= n */
+static int sc_from_shifted(sc* r, uint64_t j, int off) {
+  uint64_t v[6] = {0, 0, 0, 0, 0, 0};
+  const int li = off >> 6, bi = off & 63;
+  v[li] = j << bi;
+  if (bi) v[li + 1] = j >> (64 - bi);
+  if (v[4] | v[5]) return 0;
+  memcpy(r->d, v, 32);
+  return u256_lt(r->d, SN);
+}
+
+/* Fixed-base table sweeps: record k has u1 = j 2^off exactly (HKVO_PIN_U1),
+ * j = j0 + k step, off = 20 (t / 2) + 128 (t % 2): the scalar whose radix-2^20
+ * Booth digit in window t / 2 of half t % 2 is j (-2^19 and a carry at
+ * j = 2^19). With neg, u1 = (2^20 - j) 2^off: digit -j in that window and +1
+ * in the next (t < 12). Key d G and u2 are fixed per table, so
+ * R_j = R_(j - step) +- step 2^off G: one mixed addition per record and one
+ * inversion per block of GT_BLOCK, on up to 16 threads. */
+#define GT_BLOCK 256
+struct gtjob {
+  int t, neg, err;
+  uint64_t j0, step;
+  size_t lo, hi;
+  const sc *u2, *u2inv, *c; /* c = u2 d */
+  const ge *q, *b;          /* b = +-step 2^off G */
+  uint8_t* out;
+};
+static void gt_u1(sc* u1, const struct gtjob* g, size_t k) {
+  const uint64_t j = g->j0 + (uint64_t)k * g->step;
+  sc_from_shifted(u1, g->neg ? (1ULL << 20) - j : j, 20 * (g->t / 2) + 128 * (g->t % 2)); /* checked by the caller */
+}
+static void* gtworker(void* arg) {
+  struct gtjob* g = (struct gtjob*)arg;
+  gej pts[GT_BLOCK], cur;
+  fe pre[GT_BLOCK];
+  sc u1, k;
+  g->err = 0;
+  gt_u1(&u1, g, g->lo);
+  sc_add(&k, &u1, g->c);
+  if (sc_is_zero(&k)) { g->err = HKVO_E_INFINITY; return NULL; }
+  ecmult_gen(&cur, &k);
+  for (size_t base = g->lo; base < g->hi; base += GT_BLOCK) {
+    const size_t cnt = g->hi - base < GT_BLOCK ? g->hi - base : GT_BLOCK;
+    for (size_t i = 0; i < cnt; ++i) {
+      if (cur.inf) { g->err = HKVO_E_INFINITY; return NULL; }
+      pts[i] = cur;
+      if (i) fe_mul(&pre[i], &pre[i - 1], &cur.z);
+      else pre[0] = cur.z;
+      gej_add_ge(&cur, &cur, g->b, NULL, NULL);
+    }
+    fe inv;
+    fe_inv(&inv, &pre[cnt - 1]);
+    for (size_t i = cnt; i-- > 0;) {
+      fe zi, zi2, x;
+      if (i > 0) {
+        fe_mul(&zi, &inv, &pre[i - 1]);
+        fe_mul(&inv, &inv, &pts[i].z);
+      } else {
+        zi = inv;
+      }
+      fe_sqr(&zi2, &zi);
+      fe_mul(&x, &pts[i].x, &zi2);
+      fe_normalize(&x);
+      sc r, s, msg;
+      sc_from_fe_x(&r, &x);
+      if (sc_is_zero(&r)) { g->err = HKVO_E_R_ZERO; return NULL; }
+      sc_mul(&s, &r, g->u2inv);
+      const int high = sc_is_high(&s);
+      if (high) sc_negate(&s, &s);
+      gt_u1(&u1, g, base + i);
+      sc_mul(&msg, &u1, &s);
+      write_record(g->out + 168 * (base + i), &msg, &r, &s, g->q, high, ((base + i) & 1) == 0);
+    }
+  }
+  return NULL;
+}
+static int builder_threads(void) {
+  cpu_set_t set;
+  int n = 1;
+  if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
+  return n < 1 ? 1 : n > 16 ? 16 : n;
+}
+/* count records for j = j0, j0 + step, ... of table t (0..13), 1 <= j <= 2^19.
+ * Returns 0 or -HKVO_E_*. */
+int hkvo_fast_gtable_records_strided(int t, uint64_t j0, uint64_t step, size_t count, int neg, uint8_t* out) {
+  pthread_once(&g_once, init_tables);
+  if (count == 0) return 0;
+  if (t < 0 || t > 13 || j0 < 1 || step < 1 || step > (1u << 19) || count > (1u << 19)) return -HKVO_E_ARG;
+  const uint64_t jmax = j0 + (uint64_t)(count - 1) * step;
+  const int off = 20 * (t / 2) + 128 * (t % 2);
+  sc u1, u2, d, u2inv, c, e;
+  if (jmax > (1u << 19) || (neg && t >= 12)) return -HKVO_E_ARG;
+  if (!sc_from_shifted(&u1, neg ? (1ULL << 20) - j0 : jmax, off)) return -HKVO_E_ARG; /* the largest u1 of the call */
+  sc_filler(&d, 3, (uint64_t)t, 0);
+  sc_filler(&u2, 4, (uint64_t)t, 0);
+  sc_inverse(&u2inv, &u2);
+  sc_mul(&c, &u2, &d);
+  gej J;
+  ge q, b;
+  ecmult_gen(&J, &d);
+  ge_from_gej(&q, &J);
+  { /* step 2^off (< 2^268) mod n */
+    sc sh, st = {{step, 0, 0, 0}};
+    sc_from_shifted(&sh, 1, off);
+    sc_mul(&e, &st, &sh);
+  }
+  ecmult_gen(&J, &e);
+  ge_from_gej(&b, &J);
+  if (neg) {
+    fe_negate(&b.y, &b.y, 1);
+    fe_normalize(&b.y);
+  }
+  int nthreads = builder_threads();
+  if ((size_t)nthreads > (count + GT_BLOCK - 1) / GT_BLOCK) nthreads = (int)((count + GT_BLOCK - 1) / GT_BLOCK);
+  pthread_t th[16];
+  int created[16] = {0};
+  struct gtjob jobs[16];
+  const size_t per = (count + (size_t)nthreads - 1) / (size_t)nthreads;
+  int used = 0;
+  for (int i = 0; i < nthreads; ++i) {
+    size_t lo = (size_t)i * per, hi = lo + per;
+    if (lo >= count) break;
+    if (hi > count) hi = count;
+    jobs[i] = (struct gtjob){t, neg, 0, j0, step, lo, hi, &u2, &u2inv, &c, &q, &b, out};
+    if (pthread_create(&th[i], NULL, gtworker, &jobs[i]) == 0) created[i] = 1;
+    else gtworker(&jobs[i]);
+    used = i + 1;
+  }
+  int err = 0;
+  for (int i = 0; i < used; ++i) {
+    if (created[i]) pthread_join(th[i], NULL);
+    if (jobs[i].err && !err) err = jobs[i].err;
+  }
+  return -err;
+}
+/* the step-1 wrapper: j = j0 .. j0 + count - 1, one record per consecutive entry */
+int hkvo_fast_gtable_records(int t, uint64_t j0, size_t count, int neg, uint8_t* out) {
+  return hkvo_fast_gtable_records_strided(t, j0, 1, count, neg, out);
 }

@@ -16,7 +16,10 @@ Classes (SURVEY.md §8(c) known-answer constructions):
   r_eq_full_x_rejected the same tuple with r = R.x (>= n): compact overflow
   edge_u1 / edge_u2    keyless tuples with u1 / u2 in {1, 2, n-1, n-2, lambda,
                        n-lambda, 2^128-1, 2^128, 2^128+1, 2^129+3, 2^255,
-                       n/2, (n+1)/2, 2^32-1}
+                       n/2, (n+1)/2, 2^32-1}; keyless() flips a high s to low-S,
+                       which negates both scalars, so a record may exercise
+                       (n - u1, n - u2) instead of the value named: the exact
+                       scalars live in tests/test_gpu_chosen_scalars.py
   u1_zero / u1_zero_msg_n   msg32 = 0 / msg32 = n (msg mod n = 0), valid
   msg_ge_n             msg32 = m + n for a signature of m (reduced mod n), valid
   sum_infinity         u1*G + u2*Q = infinity: reject

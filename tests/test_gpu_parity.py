@@ -122,7 +122,10 @@ def test_glv_split(torch, ver):
         assert (s1 * k1 + s2 * k2 * o.LAMBDA - k) % o.N == 0
 
 
-def test_ecmult_g_table_source(torch, ver):
+def test_ecmult_simple_known_answers(torch, ver):
+    """Debug op ECMULT_G is ecmult_simple, the ladder hkv_gtable_kernel fills the
+    fixed-base tables with; the tables themselves are read through verify in
+    tests/test_gpu_chosen_scalars.py."""
     ks = [1, 2, 3, 128, 2**128, 5 * 2**128, o.N - 1]
     out = run_debug(torch, ver, "ECMULT_G", ks, ks)
     for i, k in enumerate(ks):

@@ -18,6 +18,7 @@ import pytest
 
 import secp256k1_oracle as o
 from conftest import GOLDEN, oracle_batch
+from recoding import G1, G2, booth, glv_residues, glv_split
 
 
 def test_curve_constants():
@@ -32,31 +33,14 @@ def test_curve_constants():
 
 def test_device_glv_constants_and_bounds():
     """The kernel's GLV split (hkv_scalar.h glv_split) restated on ints."""
-    g1 = (2**384 * o.B2 + o.N // 2) // o.N
-    g2 = (2**384 * (-o.B1) + o.N // 2) // o.N
-    assert g1 == 0x3086D221A7D46BCDE86C90E49284EB153DAA8A1471E8CA7FE893209A45DBB031
-    assert g2 == 0xE4437ED6010E88286F547FA90ABFE4C4221208AC9DF506C61571B4AE8AC47F71
+    assert G1 == 0x3086D221A7D46BCDE86C90E49284EB153DAA8A1471E8CA7FE893209A45DBB031
+    assert G2 == 0xE4437ED6010E88286F547FA90ABFE4C4221208AC9DF506C61571B4AE8AC47F71
     rng = random.Random(5)
     ks = [rng.randrange(o.N) for _ in range(3000)] + [0, 1, o.N - 1, o.LAMBDA, 2**128, 2**255, o.N // 2]
     for k in ks:
-        c1 = (k * g1 + 2**383) >> 384
-        c2 = (k * g2 + 2**383) >> 384
-        k2 = (c1 * (-o.B1) + c2 * (-o.B2)) % o.N
-        k1 = (k - k2 * o.LAMBDA) % o.N
-        m1 = o.N - k1 if k1 > o.N // 2 else k1
-        m2 = o.N - k2 if k2 > o.N // 2 else k2
+        m1, s1, m2, s2 = glv_split(k)
         assert m1 < 2**129 and m2 < 2**129
-        s1 = -1 if k1 > o.N // 2 else 1
-        s2 = -1 if k2 > o.N // 2 else 1
         assert (s1 * m1 + s2 * m2 * o.LAMBDA - k) % o.N == 0
-
-
-def booth(k, w, nwin):
-    digits = []
-    for i in range(nwin):
-        v = ((k << 1) >> (w * i)) & ((1 << (w + 1)) - 1)
-        digits.append(((v + 1) >> 1) - ((v >> w) << w))
-    return digits
 
 
 def test_top_window_merge_digit_range():
@@ -68,16 +52,10 @@ def test_top_window_merge_digit_range():
     would run the windows one by one)."""
     assert (abs(o.A1) + abs(o.A2)) // 2 < 2**128 and (abs(o.B1) + abs(o.B2)) // 2 < 2**128
     rng = random.Random(11)
-    g1 = (2**384 * o.B2 + o.N // 2) // o.N
-    g2 = (2**384 * (-o.B1) + o.N // 2) // o.N
     ks = [rng.randrange(o.N) for _ in range(3000)] + [0, 1, o.N - 1, o.LAMBDA, 2**128, 2**255, o.N // 2]
     seen_top = 0
     for k in ks:
-        c1 = (k * g1 + 2**383) >> 384
-        c2 = (k * g2 + 2**383) >> 384
-        k2 = (c1 * (-o.B1) + c2 * (-o.B2)) % o.N
-        k1 = (k - k2 * o.LAMBDA) % o.N
-        for kk in (k1, k2):
+        for kk in glv_residues(k):
             mag = o.N - kk if kk > o.N // 2 else kk
             assert mag < 2**128
             d = booth(mag, 4, 33)
