@@ -72,8 +72,13 @@ class Key:
         self.h160 = sh.hash160(self.pub)
 
 
-def push(data: bytes) -> bytes:
+def push(data: bytes, form: Optional[str] = None) -> bytes:
+    """A data push: minimal by default; form "4c" / "4d" / "4e" forces
+    OP_PUSHDATA1 / 2 / 4 (the length must fit the form)."""
     n = len(data)
+    if form is not None:
+        width = {"4c": 1, "4d": 2, "4e": 4}[form]
+        return bytes([int(form, 16)]) + n.to_bytes(width, "little") + data
     if n <= 75:
         return bytes([n]) + data
     if n <= 255:
