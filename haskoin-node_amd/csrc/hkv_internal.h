@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/hkv.h"
+#include "hkv_launch_plan.h"
 
 #define HKV_MODE_LIBSECP 0u
 #define HKV_MODE_HASKOIN 1u
@@ -84,14 +85,28 @@ enum {
 };
 
 namespace hkv {
-hipError_t launch_prologue(const void* recs, uint32_t n, uint32_t n_pad, uint32_t mode, uint32_t* im,
-                           hipStream_t st);
-// chunk: signatures per table / chain launch pair of a batch above the
-// mid-size range (qs holds chunk * (QTAB_QUADS + QTAB_ZG_QUADS) quads then)
-hipError_t launch_ecmult(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* qs,
-                         uint32_t grid, uint32_t* bits, uint32_t n_words, bool split, bool mid,
-                         unsigned long long* clk, uint32_t* aux, const void* recs, uint32_t mode, uint32_t n_cu,
-                         uint32_t chunk, hipStream_t st);
+// The launch wrappers of a verify take the batch's plan (hkv_launch_plan.h),
+// which names the kernels and their grids, and these operands. A plan the
+// wrapper cannot run gives hipErrorInvalidValue.
+struct RecOps {
+  uint32_t* im;
+  uint32_t n;
+  const uint32_t* gtab;
+  uint32_t* qs;  // plan.qs_quads quads at least
+  uint32_t* bits;
+  uint32_t n_words;
+  unsigned long long* clk;  // the clock probe, or null
+  uint32_t* aux;
+  const void* recs;
+  uint32_t mode;
+};
+struct StdOps;
+// Mid and TableChain record batches: parse, s^-1 (plan.inv_stride lanes), GLV
+hipError_t launch_prologue(const RecPlan& p, const RecOps& r, hipStream_t st);
+// the main launch of plan.shape. std_pro (Mid only): a standard-input batch
+// (the overlapped path) — std_parse, prologue, s^-1 and GLV in one lane per
+// input at the head of the mid-size ecmult kernel's lanes
+hipError_t launch_ecmult(const RecPlan& p, const RecOps& r, const StdOps* std_pro, hipStream_t st);
 hipError_t launch_gtable(uint32_t* gtab, hipStream_t st);
 // the multisig scan operands a fused launch may take over (hkv_ms_scan_kernel's);
 // counters: this call's running sum (candidates | key checks << 32), one of
@@ -152,25 +167,18 @@ struct StdOps {
   const hkv_input_job* jobs;
   int32_t forkid;
 };
-// small batches of standard inputs in one launch; with ms, the block kernel
-// (std_split_scans) also runs the multisig scan; with tx_off (the block
-// kernel only), it builds the index rows of its inputs' txs into txt itself
-// (no index launch before it)
-hipError_t launch_std_verify_split(const StdOps& o, uint32_t n, uint32_t n_pad, uint8_t* recs, uint32_t* im,
-                                   const uint32_t* gtab, uint32_t* qs, uint32_t* aux, uint32_t* bits,
-                                   uint32_t n_words, unsigned long long* clk, uint32_t n_cu, const MsScan* ms,
+// Block and Pair chunks of standard inputs in one launch (r.recs is written:
+// each input's verify record). With ms (plan.scan_in_kernel), the block kernel
+// also runs the multisig scan; with tx_off (plan.rows_in_kernel), it builds
+// the index rows of its inputs' txs into txt itself (no index launch before it)
+hipError_t launch_std_verify_split(const StdPlan& p, const StdOps& o, const RecOps& r, const MsScan* ms,
                                    const uint32_t* tx_off, hipStream_t st);
-bool std_split_scans(uint32_t n_pad, uint32_t n_cu);
-// mid-size standard-input batches (the overlapped path): std_parse, prologue,
-// s^-1 and GLV in one lane per input at the head of the mid-size ecmult
-// kernel's lanes
-hipError_t launch_std_ecmult_mid(const StdOps& o, uint32_t* im, uint32_t n, uint32_t n_pad, uint32_t* qs,
-                                 uint32_t grid, unsigned long long* clk, hipStream_t st);
-// y-free full-grid batches: u1 * G, the y0 = num / den reduction and the
-// verdict bitmap (mid: the paired-product instance; late_recs: large
-// standard-input batches, u1 and the validity from the final records first)
-hipError_t launch_finish(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* rare_ctr,
-                         uint32_t* bits, uint32_t n_words, bool mid, const void* late_recs, hipStream_t st);
+// y-free full-grid batches (Mid: the paired-product instance; TableChain):
+// u1 * G, the y0 = num / den reduction and the verdict bitmap
+// (plan.verdict_stride lanes). late_recs: large standard-input batches, u1
+// and the validity from the final records first
+hipError_t launch_finish(const RecPlan& p, const RecOps& r, uint32_t* rare_ctr, const void* late_recs,
+                         hipStream_t st);
 hipError_t launch_gen_pool(uint64_t seed, uint32_t npool, uint32_t* pool, hipStream_t st);
 hipError_t launch_gen_records(uint64_t seed, uint64_t index0, uint32_t n, const uint32_t* pool, uint32_t npool,
                               uint32_t unc_permille, uint32_t invalid_permille, void* recs, uint32_t* labels,

@@ -836,8 +836,7 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_chain_kernel(uint32_
 //     barrier P, beside the chains — u1 = m / s is the only thing that needs
 //     the message — and writes the input's verify record.
 // ---------------------------------------------------------------------------
-constexpr int PAIR_SIGS = 32;
-constexpr int PAIR_TPB = 256;
+constexpr int PAIR_TPB = 256;  // (PAIR_SIGS: hkv_layout.h)
 // phase-stamp slots (clk[4 + slot]; include/hkv.h hkv_profile_phases)
 enum : int { STAMP_START = 0, STAMP_TABLE0, STAMP_P, STAMP_CHAIN0, STAMP_A, STAMP_JOIN, STAMP_SIG, STAMP_GSUM,
              STAMP_SQRT, STAMP_TABLE1, STAMP_CHAIN1, STAMP_COUNT };
@@ -1409,8 +1408,7 @@ __global__ void __launch_bounds__(PAIR_TPB, 2) hkv_pair_split_kernel(uint32_t* _
 constexpr int BLK_K1 = HKV_BLK_K1, BLK_K2 = HKV_BLK_K2;
 static_assert(HKV_BLK_K1_HASHED == 0 || (HKV_BLK_K1_HASHED >= 2 && HKV_BLK_K1_HASHED < HKV_BLK_K2), "three segments");
 static_assert(BLK_K1 >= 2 && BLK_K1 < BLK_K2 && BLK_K2 <= NWIN - 1, "three non-empty segments");
-constexpr int BLK_SIGS = 16;
-constexpr int BLK_TPB = 256;
+constexpr int BLK_TPB = 256;  // (BLK_SIGS: hkv_layout.h)
 
 // The workgroup's 16 input txs and prevout scripts in LDS (STD): every wave's
 // parse of an input (template, pushes, DER, the key) and the signature
@@ -1868,12 +1866,7 @@ HKV_DEV bool x_matches_r(const fe& Xin, const fe& Z, const uint32_t r[8]) {
   return eq || (small_r && fe_eq_norm(t, X));
 }
 
-// signatures per lane of the verdict kernel: one Fermat den^-1 (255S + 15M,
-// a dependent chain) per lane, 3 multiplications per signature
-#ifndef HKV_VERDICT_BATCH
-#define HKV_VERDICT_BATCH 16
-#endif
-constexpr int VERDICT_BATCH = HKV_VERDICT_BATCH;
+// (VERDICT_BATCH, the verdict kernel's signatures per lane: hkv_layout.h)
 // den^-1: Bernstein-Yang safegcd mod p (hkv_safegcd.h); it replaced the
 // Fermat chain (255S + 15M): verdict kernel 160 -> 135 us at 1M
 #ifndef HKV_FINISH_WAVES
@@ -2972,96 +2965,96 @@ __global__ void __launch_bounds__(PAIR_TPB, 1) hkv_ms_tail_kernel(MsTail a) {
 }  // namespace hkv
 
 // ---------------------------------------------------------------------------
-// launch wrappers (called by hkv_api.cpp)
+// launch wrappers (called by hkv_api.cpp). Which kernels a batch runs, their
+// grids and strides are decided in hkv_launch_plan.h: the wrappers of a
+// verify switch on the plan's shape and choose nothing themselves.
 // ---------------------------------------------------------------------------
 namespace hkv {
 
 static inline uint32_t ceil_div(size_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
 
-hipError_t launch_prologue(const void* recs, uint32_t n, uint32_t n_pad, uint32_t mode, uint32_t* im,
-                           hipStream_t st) {
-  hipLaunchKernelGGL(hkv_prologue_kernel, dim3(ceil_div(n_pad, WG)), dim3(WG), 0, st,
-                     (const uint32_t*)recs, n, n_pad, mode, im);
+hipError_t launch_prologue(const RecPlan& p, const RecOps& r, hipStream_t st) {
+  hipLaunchKernelGGL(hkv_prologue_kernel, dim3(ceil_div(p.n_pad, WG)), dim3(WG), 0, st, (const uint32_t*)r.recs, r.n,
+                     p.n_pad, r.mode, r.im);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // BATCH_INV signatures per lane at large n; smaller batches keep at least
-  // 65,536 lanes (or one per signature) so the latency of the sequential
-  // batch products does not dominate
-  uint32_t stride = ceil_div(n_pad, BATCH_INV);
-  stride = stride > 65536u ? stride : (n_pad < 65536u ? n_pad : 65536u);
-  hipLaunchKernelGGL(hkv_inv_kernel, dim3(ceil_div(stride, WG)), dim3(WG), 0, st, n_pad, stride, im);
+  hipLaunchKernelGGL(hkv_inv_kernel, dim3(ceil_div(p.inv_stride, WG)), dim3(WG), 0, st, p.n_pad, p.inv_stride, r.im);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(hkv_glv_kernel, dim3(ceil_div(n_pad, WG)), dim3(WG), 0, st, n_pad, im);
+  hipLaunchKernelGGL(hkv_glv_kernel, dim3(ceil_div(p.n_pad, WG)), dim3(WG), 0, st, p.n_pad, r.im);
   return hipGetLastError();
 }
-// split: small batches — at most BLK_SIGS signatures per CU (a block) the
-// block kernel, else hkv_pair_split_kernel (PAIR_SIGS signatures per
-// workgroup); no separate prologue. mid: full-grid batches of at most 2
-// waves per SIMD, the paired-form instance at a 2-wave register allocation
-static inline bool block_batch(uint32_t n_pad, uint32_t n_cu) { return n_pad <= (uint32_t)BLK_SIGS * n_cu; }
-bool std_split_scans(uint32_t n_pad, uint32_t n_cu) { return block_batch(n_pad, n_cu); }
-// full-grid batches above the mid-size range (2a): the table and chain
-// launches over chunks of at most `chunk` signatures (a multiple of WG; qs
-// holds chunk tables and Zg slots)
-static hipError_t launch_table_chain(uint32_t* im, uint32_t n, uint32_t n_pad, uint32_t* qs, uint32_t chunk,
-                                     unsigned long long* clk, hipStream_t st) {
-  if (chunk < (uint32_t)WG || chunk % WG != 0) return hipErrorInvalidValue;
-  for (uint64_t next = 0; next < n_pad; next += chunk) {  // (64-bit: n_pad may be within a chunk of 2^32)
-    const uint32_t i0 = (uint32_t)next, cn = n_pad - i0 < chunk ? n_pad - i0 : chunk;
-    hipLaunchKernelGGL(hkv_qtable_kernel, dim3(cn / WG), dim3(WG), 0, st, (const uint32_t*)im, n, n_pad, i0, cn, qs);
+// TableChain (2a): the table and chain launches over the plan's chunks (each
+// a multiple of WG; qs holds a chunk's tables and Zg slots)
+static hipError_t launch_table_chain(const RecPlan& p, const RecOps& r, hipStream_t st) {
+  if (p.chunk_len < (uint32_t)WG || p.chunk_len % WG != 0) return hipErrorInvalidValue;
+  for (uint32_t k = 0; k < p.n_chunks; ++k) {
+    const uint32_t i0 = p.chunk(k).i0, cn = p.chunk(k).cn;
+    hipLaunchKernelGGL(hkv_qtable_kernel, dim3(cn / WG), dim3(WG), 0, st, (const uint32_t*)r.im, r.n, p.n_pad, i0, cn,
+                       r.qs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(hkv_chain_kernel, dim3(cn / WG), dim3(WG), 0, st, im, n, n_pad, i0, cn, (const uint32_t*)qs,
-                       i0 == 0 ? clk : nullptr);
+    hipLaunchKernelGGL(hkv_chain_kernel, dim3(cn / WG), dim3(WG), 0, st, r.im, r.n, p.n_pad, i0, cn,
+                       (const uint32_t*)r.qs, i0 == 0 ? r.clk : nullptr);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
-hipError_t launch_ecmult(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* qs,
-                         uint32_t grid, uint32_t* bits, uint32_t n_words, bool split, bool mid,
-                         unsigned long long* clk, uint32_t* aux, const void* recs, uint32_t mode, uint32_t n_cu,
-                         uint32_t chunk, hipStream_t st) {
-  uint32_t* rw = const_cast<uint32_t*>((const uint32_t*)recs);
-  if (split && block_batch(n_pad, n_cu))
-    hipLaunchKernelGGL(hkv_block_kernel<false>, dim3(n_pad / BLK_SIGS), dim3(BLK_TPB), 0, st, im, n, n_pad, gtab, qs,
-                       bits, n_words, aux, rw, mode, clk, StdArgs{});
-  else if (split)
-    hipLaunchKernelGGL(hkv_pair_split_kernel<false>, dim3(n_pad / PAIR_SIGS), dim3(PAIR_TPB), 0, st, im, n, n_pad,
-                       gtab, bits, n_words, aux, rw, mode, clk, StdArgs{});  // (record batches: no std operands)
-  else if (mid)
-    hipLaunchKernelGGL((hkv_ecmult_kernel<true, false>), dim3(grid), dim3(WG), 0, st, im, n, n_pad, qs, clk,
-                       StdArgs{});
-  else
-    return launch_table_chain(im, n, n_pad, qs, chunk, clk, st);
-  return hipGetLastError();
-}
 static StdArgs std_args(const StdOps& o) {
   return StdArgs{o.txs, o.n_tx, o.txt, o.scripts, o.scripts_len, o.jobs, o.forkid, nullptr, nullptr, nullptr, nullptr};
 }
-// small batches of standard inputs: parse, the Q chains, the script checks,
-// the sighash and the verdict in one launch (hkv_block_kernel<true> or
-// hkv_pair_split_kernel<true>); txt must hold the batch's tx index rows
-hipError_t launch_std_verify_split(const StdOps& o, uint32_t n, uint32_t n_pad, uint8_t* recs, uint32_t* im,
-                                   const uint32_t* gtab, uint32_t* qs, uint32_t* aux, uint32_t* bits,
-                                   uint32_t n_words, unsigned long long* clk, uint32_t n_cu, const MsScan* ms,
+// (the standard-input instance of the mid-size kernel: defined below
+// launch_gtable, so that this file's first uses of the kernel templates, which
+// order their instances in the code object, stay in the order they had)
+static hipError_t launch_mid_std(const RecPlan& p, const RecOps& r, const StdOps& o, hipStream_t st);
+hipError_t launch_ecmult(const RecPlan& p, const RecOps& r, const StdOps* std_pro, hipStream_t st) {
+  if (std_pro != nullptr && p.shape != Shape::Mid) return hipErrorInvalidValue;  // (the lane prologue is a mid-size form)
+  uint32_t* rw = const_cast<uint32_t*>((const uint32_t*)r.recs);
+  switch (p.shape) {
+    case Shape::Block:  // (record batches: no std operands)
+      hipLaunchKernelGGL(hkv_block_kernel<false>, dim3(p.grid), dim3(BLK_TPB), 0, st, r.im, r.n, p.n_pad, r.gtab, r.qs,
+                         r.bits, r.n_words, r.aux, rw, r.mode, r.clk, StdArgs{});
+      break;
+    case Shape::Pair:
+      hipLaunchKernelGGL(hkv_pair_split_kernel<false>, dim3(p.grid), dim3(PAIR_TPB), 0, st, r.im, r.n, p.n_pad, r.gtab,
+                         r.bits, r.n_words, r.aux, rw, r.mode, r.clk, StdArgs{});
+      break;
+    case Shape::Mid:
+      if (std_pro != nullptr) return launch_mid_std(p, r, *std_pro, st);
+      hipLaunchKernelGGL((hkv_ecmult_kernel<true, false>), dim3(p.grid), dim3(WG), 0, st, r.im, r.n, p.n_pad, r.qs,
+                         r.clk, StdArgs{});
+      break;
+    case Shape::TableChain: return launch_table_chain(p, r, st);
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+// Block and Pair chunks of standard inputs: parse, the Q chains, the script
+// checks, the sighash and the verdict in one launch (hkv_block_kernel<true> or
+// hkv_pair_split_kernel<true>, which reads the batch's prebuilt tx index rows)
+hipError_t launch_std_verify_split(const StdPlan& p, const StdOps& o, const RecOps& r, const MsScan* ms,
                                    const uint32_t* tx_off, hipStream_t st) {
   StdArgs sa = std_args(o);
-  if (ms != nullptr && block_batch(n_pad, n_cu)) {
-    sa.ms_desc = ms->desc;
-    sa.ms_off = ms->off;
-    sa.ms_ctr = reinterpret_cast<unsigned long long*>(ms->counters);
+  uint32_t* rw = const_cast<uint32_t*>((const uint32_t*)r.recs);
+  switch (p.shape) {
+    case Shape::Block:
+      if (ms != nullptr) {
+        sa.ms_desc = ms->desc;
+        sa.ms_off = ms->off;
+        sa.ms_ctr = reinterpret_cast<unsigned long long*>(ms->counters);
+      }
+      sa.tx_off = tx_off;  // the block kernel builds its own rows
+      hipLaunchKernelGGL(hkv_block_kernel<true>, dim3(p.n_pad / BLK_SIGS), dim3(BLK_TPB), 0, st, r.im, r.n, p.n_pad,
+                         r.gtab, r.qs, r.bits, r.n_words, r.aux, rw, (uint32_t)HKV_MODE_HASKOIN, r.clk, sa);
+      break;
+    case Shape::Pair:
+      if (tx_off != nullptr) return hipErrorInvalidValue;  // the pair kernel reads prebuilt rows
+      hipLaunchKernelGGL(hkv_pair_split_kernel<true>, dim3(p.n_pad / PAIR_SIGS), dim3(PAIR_TPB), 0, st, r.im, r.n,
+                         p.n_pad, r.gtab, r.bits, r.n_words, r.aux, rw, (uint32_t)HKV_MODE_HASKOIN, r.clk, sa);
+      break;
+    default: return hipErrorInvalidValue;  // (larger chunks: the extraction, then launch_ecmult)
   }
-  if (block_batch(n_pad, n_cu)) sa.tx_off = tx_off;  // the block kernel builds its own rows
-  else if (tx_off != nullptr) return hipErrorInvalidValue;  // the pair kernel reads prebuilt rows
-  uint32_t* rw = reinterpret_cast<uint32_t*>(recs);
-  if (block_batch(n_pad, n_cu))
-    hipLaunchKernelGGL(hkv_block_kernel<true>, dim3(n_pad / BLK_SIGS), dim3(BLK_TPB), 0, st, im, n, n_pad, gtab, qs,
-                       bits, n_words, aux, rw, (uint32_t)HKV_MODE_HASKOIN, clk, sa);
-  else
-    hipLaunchKernelGGL(hkv_pair_split_kernel<true>, dim3(n_pad / PAIR_SIGS), dim3(PAIR_TPB), 0, st, im, n, n_pad,
-                       gtab, bits, n_words, aux, rw, (uint32_t)HKV_MODE_HASKOIN, clk, sa);
   return hipGetLastError();
 }
 uint32_t ms_tail_slots(uint32_t n_cu) { return n_cu * PAIR_SIGS; }
@@ -3074,38 +3067,32 @@ hipError_t launch_gtable(uint32_t* gtab, hipStream_t st) {
                      gtab);
   return hipGetLastError();
 }
-hipError_t launch_std_ecmult_mid(const StdOps& o, uint32_t* im, uint32_t n, uint32_t n_pad, uint32_t* qs,
-                                 uint32_t grid, unsigned long long* clk, hipStream_t st) {
-  hipLaunchKernelGGL((hkv_ecmult_kernel<true, true>), dim3(grid), dim3(WG), 0, st, im, n, n_pad, qs, clk,
+static hipError_t launch_mid_std(const RecPlan& p, const RecOps& r, const StdOps& o, hipStream_t st) {
+  hipLaunchKernelGGL((hkv_ecmult_kernel<true, true>), dim3(p.grid), dim3(WG), 0, st, r.im, r.n, p.n_pad, r.qs, r.clk,
                      std_args(o));
   return hipGetLastError();
 }
-hipError_t launch_finish(uint32_t* im, uint32_t n, uint32_t n_pad, const uint32_t* gtab, uint32_t* rare_ctr,
-                         uint32_t* bits, uint32_t n_words, bool mid, const void* late_recs, hipStream_t st) {
+hipError_t launch_finish(const RecPlan& p, const RecOps& r, uint32_t* rare_ctr, const void* late_recs,
+                         hipStream_t st) {
+  if (p.shape != Shape::Mid && p.shape != Shape::TableChain) return hipErrorInvalidValue;
+  const bool paired = p.shape == Shape::Mid;  // (the paired-product instance)
   const uint32_t* lr = static_cast<const uint32_t*>(late_recs);
-  const dim3 g(n_pad / WG), b(WG);
-  if (mid && lr)
-    hipLaunchKernelGGL((hkv_finish_kernel<true, true>), g, b, 0, st, im, n, n_pad, gtab, rare_ctr, lr);
-  else if (mid)
-    hipLaunchKernelGGL((hkv_finish_kernel<true, false>), g, b, 0, st, im, n, n_pad, gtab, rare_ctr, lr);
+  const dim3 g(p.n_pad / WG), b(WG);
+  if (paired && lr)
+    hipLaunchKernelGGL((hkv_finish_kernel<true, true>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
+  else if (paired)
+    hipLaunchKernelGGL((hkv_finish_kernel<true, false>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
   else if (lr)
-    hipLaunchKernelGGL((hkv_finish_kernel<false, true>), g, b, 0, st, im, n, n_pad, gtab, rare_ctr, lr);
+    hipLaunchKernelGGL((hkv_finish_kernel<false, true>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
   else
-    hipLaunchKernelGGL((hkv_finish_kernel<false, false>), g, b, 0, st, im, n, n_pad, gtab, rare_ctr, lr);
+    hipLaunchKernelGGL((hkv_finish_kernel<false, false>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(hkv_rare_kernel, dim3(n_pad / WG), dim3(WG), 0, st, im, n_pad, (const uint32_t*)rare_ctr);
+  hipLaunchKernelGGL(hkv_rare_kernel, dim3(p.n_pad / WG), dim3(WG), 0, st, r.im, p.n_pad, (const uint32_t*)rare_ctr);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // VERDICT_BATCH signatures per lane at large n; smaller batches keep at
-  // least 65,536 lanes (or one per signature), as the s^-1 kernel does, so
-  // the per-lane inversion's latency is not serialised over 16 signatures.
-  // The stride is a multiple of WG (n_pad is).
-  uint32_t stride = ceil_div(ceil_div(n_pad, VERDICT_BATCH), WG) * WG;
-  const uint32_t min_lanes = n_pad < 65536u ? n_pad : 65536u;
-  if (stride < min_lanes) stride = min_lanes;
-  hipLaunchKernelGGL(hkv_yverdict_kernel, dim3(stride / WG), dim3(WG), 0, st, im, n_pad, stride, bits, n_words,
-                     rare_ctr);
+  hipLaunchKernelGGL(hkv_yverdict_kernel, dim3(p.verdict_stride / WG), dim3(WG), 0, st, r.im, p.n_pad,
+                     p.verdict_stride, r.bits, r.n_words, rare_ctr);
   return hipGetLastError();
 }
 hipError_t launch_gen_pool(uint64_t seed, uint32_t npool, uint32_t* pool, hipStream_t st) {
@@ -3139,8 +3126,8 @@ hipError_t launch_gen_sign(uint64_t seed, uint32_t n, const uint8_t* priv, const
                      msg_stride, sig);
   return hipGetLastError();
 }
-// The resident grid (grid_max = blocks per CU x CUs, hkv_api.cpp) sets the
-// split and mid-size thresholds and the mid-size kernel's grid (half of it).
+// The resident grid (Geometry::grid_max = blocks per CU x CUs) sets the
+// plan's thresholds between the shapes (hkv_launch_plan.h).
 // It is defined by the 4-wave allocation of the full-grid chain, 128 VGPRs:
 // HKV_ECMULT_WAVES blocks of 4 waves per CU. The query only confirms that
 // the chain kernel reaches it; a chain kernel that could hold more (fewer

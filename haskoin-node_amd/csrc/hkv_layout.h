@@ -62,6 +62,16 @@ constexpr uint32_t DIG_ZERO = (uint32_t)QBIAS | ((uint32_t)QBIAS << QDIG_BITS);
 #define HKV_BATCH_INV 16
 #endif
 constexpr int BATCH_INV = HKV_BATCH_INV;
+// signatures per lane of the verdict kernel: one Fermat den^-1 (255S + 15M,
+// a dependent chain) per lane, 3 multiplications per signature
+#ifndef HKV_VERDICT_BATCH
+#define HKV_VERDICT_BATCH 16
+#endif
+constexpr int VERDICT_BATCH = HKV_VERDICT_BATCH;
+// signatures per workgroup of the small-batch kernels (hkv_kernels.hip 2c, 2d):
+// the pair-lane split kernel takes 32 on 4 waves, the block kernel 16
+constexpr int PAIR_SIGS = 32;
+constexpr int BLK_SIGS = 16;
 constexpr uint32_t FLAG_VALID = 1u, FLAG_NEG1 = 2u, FLAG_NEG2 = 4u, FLAG_GLV_OVF = 8u;
 
 // y-free verification (every launch shape; hkv_kernels.hip §2b): the

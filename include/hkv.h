@@ -143,6 +143,16 @@ int hkv_debug_ms_scratch(hkv_ctx* ctx, int dev, size_t* bytes);
  * chunk, in signatures, in which such batches run (2^20; HKV_REC_CHUNK, read
  * at hkv_open, sets a smaller multiple of 256: a test hook). */
 int hkv_debug_q_scratch(hkv_ctx* ctx, int dev, size_t* bytes, size_t* chunk);
+/* Read-only test hook: the launch shape a batch of n (1..0xFFFFFF00) would
+ * take on device dev, from the plan the verify entry points run on; nothing is
+ * launched. kind 0: n records; kind 1: n standard inputs. out[0] = the shape
+ * of the first chunk (1 the block kernel, 2 the pair kernel, 3 the mid-size
+ * instance, 4 the table and chain launches); out[1] = for standard inputs,
+ * bit 0 the multisig scan runs in the kernel, bit 1 the kernel builds its tx
+ * index rows, bit 2 the hash half overlaps the Q chains (0 for records);
+ * out[2] = the first chunk's length (records: padded to 256; the chunk of the
+ * table and chain launches); out[3] = the number of chunks. */
+int hkv_debug_launch_shape(hkv_ctx* ctx, int dev, uint32_t kind, size_t n, uint32_t out[4]);
 /* Read-only test hook: what device dev's last multisig tail launch saw and
  * did, read after every call enqueued so far has completed. out[0] = the
  * scan's total it ran on (candidate records | key-check records << 32),

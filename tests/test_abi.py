@@ -61,6 +61,7 @@ def test_bad_arguments_rejected_without_device(lib):
     assert lib.hkv_debug_ms_window(None, 0, 64, 64) == -1
     assert lib.hkv_debug_ms_scratch(None, 0, ctypes.byref(ctypes.c_size_t())) == -1
     assert lib.hkv_debug_ms_tail_counts(None, 0, (ctypes.c_uint64 * 3)()) == -1
+    assert lib.hkv_debug_launch_shape(None, 0, 0, 4096, (ctypes.c_uint32 * 4)()) == -1
     assert lib.hkv_device_fault(None, 0, ctypes.byref(ctypes.c_uint32())) == -1
 
 

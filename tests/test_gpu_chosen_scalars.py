@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import chosen_scalars as cs
+import launch_shapes
 import recoding as rc
 from conftest import fast_batch, host_threads
 
@@ -98,10 +99,13 @@ def directed(lib):
     return batch, [names[i if t < 0 else t] + ("" if t < 0 else "/flipped") for i, t in enumerate(twin_of)], twin_of < 0
 
 
-# The shapes below assume an MI355X: 256 CUs, a resident grid of 262,144 lanes. n_pad (n rounded up to 256)
-# <= 4,096 (16 signatures per CU) runs hkv_block_kernel, <= 32,768 (grid / 8) hkv_pair_split_kernel,
-# <= 131,072 (grid / 2) the mid-size hkv_ecmult_kernel instance, above it hkv_qtable_kernel + hkv_chain_kernel
-# (hkv_api.cpp split_batch / mid_batch, hkv_kernels.hip launch_ecmult).
+# The shape each n takes is the library's plan (haskoin-node_amd/csrc/hkv_launch_plan.h), asked through
+# hkv_debug_launch_shape: hkv_block_kernel, hkv_pair_split_kernel, the mid-size hkv_ecmult_kernel instance,
+# hkv_qtable_kernel + hkv_chain_kernel.
+SHAPE_OF_N = {0: launch_shapes.BLOCK, 8_192: launch_shapes.PAIR, 33_024: launch_shapes.MID,
+              131_136: launch_shapes.TABLE_CHAIN}
+
+
 @pytest.mark.parametrize("n", [0, 8_192, 33_024, 131_136])
 def test_directed_set_on_every_launch_shape(torch, ver, lib, directed, n):
     """S alone (1,835 records with the twins: the block kernel, which cuts each
@@ -111,10 +115,10 @@ def test_directed_set_on_every_launch_shape(torch, ver, lib, directed, n):
     n = 33,024 (the mid-size instance) and n = 131,136 (table and chain
     launches): both modes, every verdict the checker's, every record of S
     accepted and every flipped twin rejected."""
-    assert torch.cuda.get_device_properties(0).multi_processor_count == 256  # the thresholds above
     recs, names, accepted = directed
     ns = len(names)
-    assert ns <= 4_096  # S alone stays a block-kernel batch
+    assert ns <= 4_096
+    assert launch_shapes.records(ver, n or ns)[0] == SHAPE_OF_N[n]  # (S alone: a block-kernel batch)
     at = np.arange(ns)
     batch = recs
     if n:

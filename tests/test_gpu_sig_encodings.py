@@ -26,6 +26,7 @@ import random
 
 import pytest
 
+import launch_shapes
 import sighash_oracle as sh
 import sig_encodings as se
 from conftest import oracle_batch
@@ -103,6 +104,8 @@ def test_alone_block_kernel(torch, ver, coracle, forkid):  # noqa: F811
     import hkv
     table, raw, jobs, exp = _table(forkid)
     assert len(jobs) <= 16 * 256
+    assert launch_shapes.std_inputs(ver, len(jobs))[:2] == (
+        launch_shapes.BLOCK, launch_shapes.SCAN_IN_KERNEL | launch_shapes.ROWS_IN_KERNEL)
     want = _want(coracle, forkid)
     _check("host", table, exp, want, hkv.verify_std_inputs(ver, raw, jobs, forkid), None)
     got, recs = _device_verify_std(torch, ver, raw, jobs, forkid, records=True)
@@ -124,8 +127,9 @@ def test_shuffled_into_block(torch, ver, coracle, n_fill, forkid):  # noqa: F811
     order = list(range(len(all_jobs)))
     random.Random(0x5348 + n_fill).shuffle(order)
     jobs_sh = [all_jobs[k] for k in order]
-    lo, hi = (32768, 131072) if n_fill >= 20000 else (16 * 256, 32768)
-    assert lo < len(jobs_sh) <= hi
+    # one chunk of the shape meant (the library's plan: hkv_launch_plan.h)
+    want_shape = ((launch_shapes.MID, launch_shapes.OVERLAP) if n_fill >= 20000 else (launch_shapes.PAIR, 0))
+    assert launch_shapes.std_inputs(ver, len(jobs_sh)) == want_shape + (len(jobs_sh), 1)
     where = {k - len(bjobs): pos for pos, k in enumerate(order) if k >= len(bjobs)}
     fill = [pos for pos, k in enumerate(order) if k < len(bjobs)]
 

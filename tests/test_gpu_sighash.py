@@ -10,6 +10,7 @@ import random
 import numpy as np
 import pytest
 
+import launch_shapes
 import secp256k1_oracle as o
 import sighash_oracle as sh
 import txgen
@@ -466,7 +467,15 @@ def test_std_inputs_full_grid_overlap_vs_oracle(torch, ver, coracle, n_fill, for
     order = list(range(len(all_jobs)))
     rng.shuffle(order)
     jobs_sh = [all_jobs[k] for k in order]
-    assert len(jobs_sh) > (131072 if n_fill >= 75000 else 32768 if n_fill >= 20000 else 16 * 256)
+    # the shape meant, from the library's plan (hkv_launch_plan.h): first chunk's shape, its flags, chunks
+    shape = launch_shapes.std_inputs(ver, len(jobs_sh))
+    if n_fill >= 75000:
+        assert shape == (launch_shapes.MID, launch_shapes.OVERLAP, shape[2], 2) and shape[2] < len(jobs_sh)
+        assert launch_shapes.std_inputs(ver, len(jobs_sh) - shape[2])[0] == launch_shapes.PAIR
+    elif n_fill >= 20000:
+        assert shape == (launch_shapes.MID, launch_shapes.OVERLAP, len(jobs_sh), 1)
+    else:
+        assert shape == (launch_shapes.PAIR, 0, len(jobs_sh), 1)
     got, recs = _device_verify_std(torch, ver, all_raw, jobs_sh, forkid, records=True)
     bad = [pos for pos, k in enumerate(order)
            if k >= len(bjobs) and recs[pos * 168:(pos + 1) * 168] != exp_small[k - len(bjobs)]]
