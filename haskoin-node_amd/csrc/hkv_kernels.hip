@@ -60,6 +60,61 @@ HKV_DEV void rec_be256(uint32_t out[8], const uint32_t* w, int off) {
 __constant__ static const uint32_t PMN[8] = {0x2FC9BAEEu, 0x402DA172u, 0x50B75FC4u, 0x45512319u, 1u, 0, 0, 0};
 
 // ---------------------------------------------------------------------------
+// the intermediates (hkv_layout.h): a view of im or aux, the one place that
+// forms [word row * n_pad + signature]. The signature index is the lane's
+// 32-bit one, widened here at the use. One-word access keeps the caller's
+// index type I for the two sites that form theirs in 64 bits: the inverse
+// kernel's i - stride and the rare list's base + rank.
+// The hand-offs that move several fields of one lane together (B', A, the
+// join inputs) stay loops over get / put at their sites: written as shared
+// functions over these methods they compiled to other code in the chain,
+// mid-size, finish, pair, block and tail kernels (profiles/r12_im_layout/).
+// Where the view is held matters to the compiler too. A named view in the
+// body of hkv_ecmult_kernel or hkv_chain_kernel, or as finish_lane's
+// parameter, changed those kernels' loops, and so did any form of the
+// verdict kernel but the one below: the two kernels index im themselves at
+// their five sites, finish_lane builds its view at each use from its own
+// im, n_pad, and the verdict kernel calls ld8 / st8 on its im. All other
+// code holds a view and passes it on.
+// ---------------------------------------------------------------------------
+template <class W>  // uint32_t, or const uint32_t for a read-only view
+struct SoA {
+  W* p;
+  uint32_t n_pad;
+  // (the row is never negative; saying so keeps the product's sign known)
+  template <class I>
+  HKV_DEV size_t at(Field f, int k, I i) const { return (size_t)(uint32_t)(f.off + k) * n_pad + i; }
+  // word k of field f
+  template <class I>
+  HKV_DEV uint32_t get(Field f, int k, I i) const { return p[at(f, k, i)]; }
+  template <class I>
+  HKV_DEV void put(Field f, int k, I i, uint32_t v) const { p[at(f, k, i)] = v; }
+  template <class I>
+  HKV_DEV uint32_t get(Field f, I i) const { return get(f, 0, i); }
+  template <class I>
+  HKV_DEV void put(Field f, I i, uint32_t v) const { put(f, 0, i, v); }
+  // an eight-limb value
+  // (the eight-limb move on a bare pointer: get8 / put8, and the verdict kernel directly)
+  static HKV_DEV void ld8(const uint32_t* __restrict__ q, uint32_t n_pad, int w, uint32_t i, uint32_t* v) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = q[(size_t)(w + k) * n_pad + i];
+  }
+  static HKV_DEV void st8(uint32_t* __restrict__ q, uint32_t n_pad, int w, uint32_t i, const uint32_t* v) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) q[(size_t)(w + k) * n_pad + i] = v[k];
+  }
+  HKV_DEV void get8(Field f, uint32_t i, uint32_t* v) const { ld8(p, n_pad, f.off, i, v); }
+  HKV_DEV void put8(Field f, uint32_t i, const uint32_t* v) const { st8(p, n_pad, f.off, i, v); }
+  HKV_DEV void get8(Field f, uint32_t i, fe& a) const { get8(f, i, a.v); }
+  HKV_DEV void get8(Field f, uint32_t i, sc& a) const { get8(f, i, a.v); }
+  HKV_DEV void put8(Field f, uint32_t i, const fe& a) const { put8(f, i, a.v); }
+  HKV_DEV void put8(Field f, uint32_t i, const sc& a) const { put8(f, i, a.v); }
+  HKV_DEV operator SoA<const uint32_t>() const { return {p, n_pad}; }
+};
+using SoAView = SoA<uint32_t>;
+using SoACView = SoA<const uint32_t>;
+
+// ---------------------------------------------------------------------------
 // 1. prologue
 // ---------------------------------------------------------------------------
 #ifndef HKV_PROLOGUE_WAVES
@@ -179,20 +234,21 @@ __global__ void __launch_bounds__(WG, HKV_PROLOGUE_WAVES) hkv_prologue_kernel(co
   ok = ok && !u256_is_zero(r.v) && !u256_is_zero(s.v);
   sc_cond_sub_n(m.v);  // m = msg32 mod n (msg32 < 2^256 < 2n)
 
-  // --- pubkey: secp256k1_ec_pubkey_parse (y-free: y stays implicit, IM_QY = w)
-  fe x, y;
+  // --- pubkey: secp256k1_ec_pubkey_parse (y-free: y stays implicit, w = x^3 + 7 goes to IM_W)
+  fe x, wv;
   uint32_t pflags = 0;
-  ok = pubkey_parse_rec_w(w, x, y, pflags) && ok;
+  ok = pubkey_parse_rec_w(w, x, wv, pflags) && ok;
 
   const uint32_t flags = (ok ? FLAG_VALID : 0u) | pflags;
-  im[(size_t)IM_FLAGS * n_pad + i] = flags;
+  const SoAView iv = {im, n_pad};
+  iv.put(IM_FLAGS, i, flags);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    im[(size_t)(IM_QX + k) * n_pad + i] = x.v[k];
-    im[(size_t)(IM_QY + k) * n_pad + i] = y.v[k];
-    im[(size_t)(IM_R + k) * n_pad + i] = r.v[k];
-    im[(size_t)(IM_S + k) * n_pad + i] = s.v[k];
-    im[(size_t)(IM_M + k) * n_pad + i] = m.v[k];
+    iv.put(IM_QX, k, i, x.v[k]);
+    iv.put(IM_W, k, i, wv.v[k]);
+    iv.put(IM_R, k, i, r.v[k]);
+    iv.put(IM_S, k, i, s.v[k]);
+    iv.put(IM_M, k, i, m.v[k]);
   }
 }
 
@@ -226,15 +282,6 @@ HKV_DEV void key_check_lane(const uint32_t* __restrict__ recs, uint32_t i, uint3
 //     signatures per thread (strided for coalescing), then u1 = m/s,
 //     u2 = r/s and the GLV split of u2.
 // ---------------------------------------------------------------------------
-HKV_DEV void im_load8(const uint32_t* __restrict__ im, uint32_t n_pad, int w, uint32_t i, uint32_t* v) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = im[(size_t)(w + k) * n_pad + i];
-}
-HKV_DEV void im_store8(uint32_t* __restrict__ im, uint32_t n_pad, int w, uint32_t i, const uint32_t* v) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) im[(size_t)(w + k) * n_pad + i] = v[k];
-}
-
 template <int L>
 HKV_DEV void shr_bits(uint32_t* a, int b) {
 #pragma unroll
@@ -244,7 +291,7 @@ HKV_DEV void shr_bits(uint32_t* a, int b) {
 // Radix-2^QW / radix-2^20 Booth recoding (LSB first, MSB-first consumption in
 // the ecmult kernel): d = ((v + 1) >> 1) - ((v >> W) << W), v = bits
 // [pos-1, pos+W-1]; sum_w d_w 2^(QW w) reproduces the scalar (< 2^129).
-HKV_DEV void write_qdigits(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, uint32_t* S1, uint32_t* S2) {
+HKV_DEV void write_qdigits(SoAView iv, uint32_t i, uint32_t* S1, uint32_t* S2) {
   constexpr uint32_t QM = (1u << QW) - 1u;
   uint32_t p1 = 0, p2 = 0;
 #pragma unroll 1
@@ -256,10 +303,10 @@ HKV_DEV void write_qdigits(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i
     shr_bits<5>(S2, QW);
     const int d1 = (int)((v1 + 1u) >> 1) - (int)((v1 >> QW) << QW);
     const int d2 = (int)((v2 + 1u) >> 1) - (int)((v2 >> QW) << QW);
-    im[(size_t)(IM_DIG + w) * n_pad + i] = (uint32_t)(d1 + QBIAS) | ((uint32_t)(d2 + QBIAS) << QDIG_BITS);
+    iv.put(IM_DIG, w, i, (uint32_t)(d1 + QBIAS) | ((uint32_t)(d2 + QBIAS) << QDIG_BITS));
   }
 }
-HKV_DEV void write_gdigits(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, uint32_t* SL, uint32_t* SH) {
+HKV_DEV void write_gdigits(SoAView iv, uint32_t i, uint32_t* SL, uint32_t* SH) {
   uint32_t pl = 0, ph = 0;
 #pragma unroll 1
   for (int j = 0; j < GWIN; ++j) {
@@ -271,14 +318,9 @@ HKV_DEV void write_gdigits(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i
     shr_bits<4>(SH, GTAB_W);
     const int dl = (int)((vl + 1u) >> 1) - (int)((vl >> GTAB_W) << GTAB_W);
     const int dh = (int)((vh + 1u) >> 1) - (int)((vh >> GTAB_W) << GTAB_W);
-    im[(size_t)(IM_GDIG + 2 * j) * n_pad + i] = (uint32_t)(dl < 0 ? -dl : dl) | (dl < 0 ? GD_NEG : 0u);
-    im[(size_t)(IM_GDIG + 2 * j + 1) * n_pad + i] = (uint32_t)(dh < 0 ? -dh : dh) | (dh < 0 ? GD_NEG : 0u);
+    iv.put(IM_GDIG, 2 * j, i, (uint32_t)(dl < 0 ? -dl : dl) | (dl < 0 ? GD_NEG : 0u));
+    iv.put(IM_GDIG, 2 * j + 1, i, (uint32_t)(dh < 0 ? -dh : dh) | (dh < 0 ? GD_NEG : 0u));
   }
-}
-HKV_DEV void write_digits(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, uint32_t* S1, uint32_t* S2,
-                          uint32_t* SL, uint32_t* SH) {
-  write_qdigits(im, n_pad, i, S1, S2);
-  write_gdigits(im, n_pad, i, SL, SH);
 }
 
 // (at one wave per SIMD the loop is load-latency bound: each iteration's
@@ -286,6 +328,7 @@ HKV_DEV void write_digits(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i,
 __global__ void __launch_bounds__(WG) hkv_inv_kernel(uint32_t n_pad, uint32_t stride, uint32_t* __restrict__ im) {
   const uint32_t t = blockIdx.x * WG + threadIdx.x;
   if (t >= stride) return;
+  const SoAView iv = {im, n_pad};
   // forward: prefix products c_k = s_0 * ... * s_k (invalid lanes use s = 1)
   sc c;
   sc_set_u32(c, 1);
@@ -293,8 +336,8 @@ __global__ void __launch_bounds__(WG) hkv_inv_kernel(uint32_t n_pad, uint32_t st
   {
     sc sv;
     uint32_t fl = 0;
-    im_load8(im, n_pad, IM_S, t, sv.v);  // t < stride <= n_pad
-    fl = im[(size_t)IM_FLAGS * n_pad + t];
+    iv.get8(IM_S, t, sv);  // t < stride <= n_pad
+    fl = iv.get(IM_FLAGS, t);
 #pragma unroll 1
     for (int k = 0; k < BATCH_INV; ++k) {
       const uint32_t i = t + (uint32_t)k * stride;
@@ -304,12 +347,12 @@ __global__ void __launch_bounds__(WG) hkv_inv_kernel(uint32_t n_pad, uint32_t st
       sc sn;
       uint32_t fn = 0;
       if (k + 1 < BATCH_INV && inext < n_pad) {
-        im_load8(im, n_pad, IM_S, inext, sn.v);
-        fn = im[(size_t)IM_FLAGS * n_pad + inext];
+        iv.get8(IM_S, inext, sn);
+        fn = iv.get(IM_FLAGS, inext);
       }
       if (!(fl & FLAG_VALID)) sc_set_u32(sv, 1);
       sc_mul(c, c, sv);
-      im_store8(im, n_pad, IM_C, i, c.v);
+      iv.put8(IM_C, i, c);
       sv = sn;
       fl = fn;
     }
@@ -322,23 +365,23 @@ __global__ void __launch_bounds__(WG) hkv_inv_kernel(uint32_t n_pad, uint32_t st
     int k = kn - 1;
     uint32_t i = t + (uint32_t)k * stride;
     sc prev, sv;
-    uint32_t fl = im[(size_t)IM_FLAGS * n_pad + i];
-    im_load8(im, n_pad, IM_S, i, sv.v);
-    if (k > 0) im_load8(im, n_pad, IM_C, i - stride, prev.v);
+    uint32_t fl = iv.get(IM_FLAGS, i);
+    iv.get8(IM_S, i, sv);
+    if (k > 0) iv.get8(IM_C, i - stride, prev);
 #pragma unroll 1
     for (; k >= 0; --k) {
       i = t + (uint32_t)k * stride;
       sc pn, sn;
       uint32_t fn = 0;
       if (k > 0) {  // the next (lower) signature's operands
-        fn = im[(size_t)IM_FLAGS * n_pad + i - stride];
-        im_load8(im, n_pad, IM_S, i - stride, sn.v);
-        if (k > 1) im_load8(im, n_pad, IM_C, i - 2 * stride, pn.v);
+        fn = iv.get(IM_FLAGS, (size_t)i - stride);  // (formed in 64 bits, as it always was)
+        iv.get8(IM_S, i - stride, sn);
+        if (k > 1) iv.get8(IM_C, i - 2 * stride, pn);
       }
       if (k == 0) sc_set_u32(prev, 1);
       sc sinv;
       sc_mul(sinv, inv, prev);
-      im_store8(im, n_pad, IM_C, i, sinv.v);
+      iv.put8(IM_C, i, sinv);
       if (!(fl & FLAG_VALID)) sc_set_u32(sv, 1);
       sc_mul(inv, inv, sv);
       prev = pn;
@@ -349,10 +392,10 @@ __global__ void __launch_bounds__(WG) hkv_inv_kernel(uint32_t n_pad, uint32_t st
 }
 
 // 1c. per signature: u1 = m/s, u2 = r/s, GLV split of u2, Booth digits.
-HKV_DEV void glv_lane(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, uint32_t flags, const sc& sinv) {
+HKV_DEV void glv_lane(SoAView iv, uint32_t i, uint32_t flags, const sc& sinv) {
   sc m, r, u1, u2;
-  im_load8(im, n_pad, IM_M, i, m.v);
-  im_load8(im, n_pad, IM_R, i, r.v);
+  iv.get8(IM_M, i, m);
+  iv.get8(IM_R, i, r);
   sc_mul(u1, m, sinv);
   sc_mul(u2, r, sinv);
   uint32_t k1[5], k2[5];
@@ -360,22 +403,24 @@ HKV_DEV void glv_lane(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, uin
   const bool glv_ok = glv_split(u2, k1, n1, k2, n2);
   uint32_t f = flags | (n1 ? FLAG_NEG1 : 0u) | (n2 ? FLAG_NEG2 : 0u) | (glv_ok ? 0u : FLAG_GLV_OVF);
   if (!glv_ok) f &= ~FLAG_VALID;  // unreachable for a correct basis; fail closed
-  im[(size_t)IM_FLAGS * n_pad + i] = f;
+  iv.put(IM_FLAGS, i, f);
   const bool use = (f & FLAG_VALID) != 0;
   uint32_t S1[5], S2[5], SL[4], SH[4];
 #pragma unroll
   for (int q = 0; q < 5; ++q) { S1[q] = use ? k1[q] : 0u; S2[q] = use ? k2[q] : 0u; }
 #pragma unroll
   for (int q = 0; q < 4; ++q) { SL[q] = use ? u1.v[q] : 0u; SH[q] = use ? u1.v[4 + q] : 0u; }
-  write_digits(im, n_pad, i, S1, S2, SL, SH);
+  write_qdigits(iv, i, S1, S2);
+  write_gdigits(iv, i, SL, SH);
 }
 __global__ void __launch_bounds__(WG) hkv_glv_kernel(uint32_t n_pad, uint32_t* __restrict__ im) {
   const uint32_t i = blockIdx.x * WG + threadIdx.x;
   if (i >= n_pad) return;
-  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  const SoAView iv = {im, n_pad};
+  const uint32_t flags = iv.get(IM_FLAGS, i);
   sc sinv;
-  im_load8(im, n_pad, IM_C, i, sinv.v);
-  glv_lane(im, n_pad, i, flags, sinv);
+  iv.get8(IM_C, i, sinv);
+  glv_lane(iv, i, flags, sinv);
 }
 
 // 1c'. large standard-input batches (hkv_api.cpp enqueue_std_chunk): the
@@ -385,8 +430,7 @@ __global__ void __launch_bounds__(WG) hkv_glv_kernel(uint32_t n_pad, uint32_t* _
 //      ecmult kernel writes B' over the Q digits only). A record the hash half
 //      zeroed (a failed HASH160 / script check) makes the lane invalid.
 //      Returns the lane's flags.
-HKV_DEV uint32_t late_u1_lane(const uint32_t* __restrict__ recs, uint32_t i, uint32_t n_pad, uint32_t* __restrict__ im,
-                              uint32_t f) {
+HKV_DEV uint32_t late_u1_lane(const uint32_t* __restrict__ recs, uint32_t i, SoAView iv, uint32_t f) {
   const uint32_t* w = recs + (size_t)i * REC_WORDS;
   if ((w[24] & 0xFFu) == 0u) f &= ~FLAG_VALID;
   const bool use = (f & FLAG_VALID) != 0;
@@ -394,31 +438,28 @@ HKV_DEV uint32_t late_u1_lane(const uint32_t* __restrict__ recs, uint32_t i, uin
 #pragma unroll
   for (int j = 0; j < 8; ++j) m.v[7 - j] = __builtin_bswap32(w[j]);
   sc_cond_sub_n(m.v);
-  im_load8(im, n_pad, IM_C, i, sinv.v);
+  iv.get8(IM_C, i, sinv);
   sc_mul(u1, m, sinv);
   uint32_t SL[4], SH[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) { SL[q] = use ? u1.v[q] : 0u; SH[q] = use ? u1.v[4 + q] : 0u; }
-  write_gdigits(im, n_pad, i, SL, SH);
+  write_gdigits(iv, i, SL, SH);
   return f;
 }
 
 // ---------------------------------------------------------------------------
-// 1d. small batches (the split ecmult's range, e.g. one block): no separate
-//     prologue launch; waves 4-5 of each split-ecmult workgroup parse the
-//     signatures (below) while waves 0-3 parse the keys and build their
-//     Q tables.
+// 1d. small batches (a block) and the standard-input lane prologue (1e): no
+//     separate prologue launch. One lane runs a signature's scalar work,
+//     per-lane s^-1 included, in two halves: the small-batch kernels' signature
+//     wave (2c, 2d: wave 2) runs the u2 half before the barrier that releases
+//     the chain waves and the u1 half after it.
 // ---------------------------------------------------------------------------
-// The signature half of a split workgroup (waves 4-5): parse r, s, m, apply
-// the mode's high-S policy,
-// s^-1, u1 = m/s, u2 = r/s, the GLV split and the Booth digits; stores the
-// digits and r for lane i.
 // The u2 half of a signature: compact-range checks, the mode's high-S policy,
 // s^-1, u2 = r/s, the GLV split of u2, the Q digits, r -> im. ok is the
 // caller's validity so far (updated); sinv is s^-1 (of 1 when !ok) for the u1
 // half (sig_lane_g).
-HKV_DEV void sig_lane_q(sc r, sc s, uint32_t mode, uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, bool& ok,
-                        bool& glv_ok, bool& n1, bool& n2, sc& sinv) {
+HKV_DEV void sig_lane_q(sc r, sc s, uint32_t mode, SoAView iv, uint32_t i, bool& ok, bool& glv_ok, bool& n1, bool& n2,
+                        sc& sinv) {
   ok = ok && u256_lt(r.v, SC_N) && u256_lt(s.v, SC_N);
   const bool high = sc_is_high(s);
   if (mode == HKV_MODE_HASKOIN) {
@@ -439,19 +480,19 @@ HKV_DEV void sig_lane_q(sc r, sc s, uint32_t mode, uint32_t* __restrict__ im, ui
   uint32_t S1[5], S2[5];
 #pragma unroll
   for (int q = 0; q < 5; ++q) { S1[q] = use ? k1[q] : 0u; S2[q] = use ? k2[q] : 0u; }
-  write_qdigits(im, n_pad, i, S1, S2);
+  write_qdigits(iv, i, S1, S2);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) im[(size_t)(IM_R + k) * n_pad + i] = r.v[k];
+  for (int k = 0; k < 8; ++k) iv.put(IM_R, k, i, r.v[k]);
 }
 // The u1 half: m = msg32 mod n, u1 = m / s, the G digits (zero unless use).
-HKV_DEV void sig_lane_g(sc m, const sc& sinv, bool use, uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i) {
+HKV_DEV void sig_lane_g(sc m, const sc& sinv, bool use, SoAView iv, uint32_t i) {
   sc_cond_sub_n(m.v);  // m = msg32 mod n
   sc u1;
   sc_mul(u1, m, sinv);
   uint32_t SL[4], SH[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) { SL[q] = use ? u1.v[q] : 0u; SH[q] = use ? u1.v[4 + q] : 0u; }
-  write_gdigits(im, n_pad, i, SL, SH);
+  write_gdigits(iv, i, SL, SH);
 }
 // flags as the full-grid kernels leave them (hkv_glv_kernel)
 HKV_DEV uint32_t split_flags(bool ok, uint32_t pk_ok, bool glv_ok, bool n1, bool n2) {
@@ -481,7 +522,7 @@ struct StdArgs {
 };
 // the standard-input lane prologue (1e) run at the head of the mid-size
 // ecmult kernel's lane (defined below, after the std parse helpers)
-HKV_DEV void std_lane_prologue(uint32_t i, uint32_t n, uint32_t n_pad, uint32_t* __restrict__ im, const StdArgs& sa);
+HKV_DEV void std_lane_prologue(uint32_t i, uint32_t n, SoAView iv, const StdArgs& sa);
 
 // ---------------------------------------------------------------------------
 // 2. ecmult + x compare
@@ -517,18 +558,17 @@ HKV_DEV void ec_accumulate(gej& acc, bool& inf, const fe& az, const fe& tx, cons
 }
 
 template <bool ILP = false>
-HKV_DEV void gsum_lane(const uint32_t* __restrict__ im, uint32_t n_pad, const uint32_t* __restrict__ gtab, uint32_t i,
-                       bool valid, gej& A, bool& ainf);
+HKV_DEV void gsum_lane(SoACView iv, const uint32_t* __restrict__ gtab, uint32_t i, bool valid, gej& A, bool& ainf);
 HKV_DEV void gej_add_var(gej& acc, bool& inf, const gej& b, bool binf);
 HKV_DEV bool x_matches_r(const fe& Xin, const fe& Z, const uint32_t r[8]);
 
-// the lane's key as Q' = (x w, w^2) on E_w (IM_QY holds w = x^3 + 7)
-HKV_DEV void lane_q(ge& q, const uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, bool valid) {
+// the lane's key as Q' = (x w, w^2) on E_w (w = x^3 + 7)
+HKV_DEV void lane_q(ge& q, SoACView iv, uint32_t i, bool valid) {
   fe x, w;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    x.v[k] = im[(size_t)(IM_QX + k) * n_pad + i];
-    w.v[k] = im[(size_t)(IM_W + k) * n_pad + i];
+    x.v[k] = iv.get(IM_QX, k, i);
+    w.v[k] = iv.get(IM_W, k, i);
   }
   fe_mul(q.x, x, w);
   fe_sqr(q.y, w);
@@ -602,13 +642,13 @@ HKV_DEV void qtable_build(const ge& q, uint32_t* __restrict__ qs, uint32_t n_lan
 // latency. signs: the lane's GLV signs (bit 0: k1, bit 1: k2), read once per
 // term from the caller's LDS slot.
 template <bool ILP>
-HKV_DEV void q_chain(gej& acc, bool& inf, const uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i, bool valid,
-                     const uint32_t* __restrict__ qs, uint32_t n_lanes, uint32_t lane, const uint32_t& signs) {
+HKV_DEV void q_chain(gej& acc, bool& inf, SoACView iv, uint32_t i, bool valid, const uint32_t* __restrict__ qs,
+                     uint32_t n_lanes, uint32_t lane, const uint32_t& signs) {
   inf = true;
   fe_set_zero(acc.x);
   fe_set_zero(acc.y);
   fe_set_zero(acc.z);
-  uint32_t dw = valid ? im[(size_t)(IM_DIG + NWIN - 1) * n_pad + i] : DIG_ZERO;
+  uint32_t dw = valid ? iv.get(IM_DIG, NWIN - 1, i) : DIG_ZERO;
   int win = NWIN - 1;
   bool dbl = false;       // the first window starts from infinity: no doublings
   int x1 = 0, x2 = 0;     // the merged top window's second terms (pair_chain)
@@ -617,7 +657,7 @@ HKV_DEV void q_chain(gej& acc, bool& inf, const uint32_t* __restrict__ im, uint3
     // the top two windows as one digit in [0, 16] per half, taken as
     // min(m, 8) + (m - 8)+ (pair_chain): two additions where every wave
     // ran the second window's 4 doublings (5 % of the halves reach 2^127)
-    const uint32_t dw2 = valid ? im[(size_t)(IM_DIG + NWIN - 2) * n_pad + i] : DIG_ZERO;
+    const uint32_t dw2 = valid ? iv.get(IM_DIG, NWIN - 2, i) : DIG_ZERO;
     const int t1 = (((int)(dw & QDIG_MASK) - QBIAS) << QW) + (int)(dw2 & QDIG_MASK) - QBIAS;
     const int t2 = (((int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS) << QW) + (int)((dw2 >> QDIG_BITS) & QDIG_MASK) - QBIAS;
     if (!__any(t1 < 0 || t1 > 2 * QBIAS || t2 < 0 || t2 > 2 * QBIAS)) {
@@ -632,7 +672,7 @@ HKV_DEV void q_chain(gej& acc, bool& inf, const uint32_t* __restrict__ im, uint3
 #pragma unroll 1
   for (; win >= 0; --win) {
     const int d1 = (int)(dw & QDIG_MASK) - QBIAS, d2 = (int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS;
-    const uint32_t dw_next = (win > 0 && valid) ? im[(size_t)(IM_DIG + win - 1) * n_pad + i] : DIG_ZERO;
+    const uint32_t dw_next = (win > 0 && valid) ? iv.get(IM_DIG, win - 1, i) : DIG_ZERO;
     if (dbl) {
 #pragma unroll 1
       for (int d = 0; d < QW; ++d) {
@@ -666,6 +706,17 @@ HKV_DEV void q_chain(gej& acc, bool& inf, const uint32_t* __restrict__ im, uint3
   }
 }
 
+// Optional clock probe (hkv_profile_clock): shader-clock and constant-rate
+// counters into clk[slot], clk[slot + 1] around block 0's work (slot 0 at its
+// start, 2 at its end), so bench.py prices the roofline at the clock the
+// launch actually ran at.
+HKV_DEV void clock_probe(unsigned long long* __restrict__ clk, int slot) {
+  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+    clk[slot] = clock64();
+    clk[slot + 1] = wall_clock64();
+  }
+}
+
 // ILP: the paired-product group forms; full-grid launches of mid-size
 // batches (at most 2 waves per SIMD: 32k-131k signatures) take the <true>
 // instance, which is allocated for 2 waves per SIMD (no spill). Larger
@@ -692,18 +743,16 @@ __global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict_
   // optional clock probe (hkv_profile_clock): shader-clock and constant-rate
   // counters around block 0's work, so bench.py prices the roofline at the
   // clock the launch actually ran at
-  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    clk[0] = clock64();
-    clk[1] = wall_clock64();
-  }
+  clock_probe(clk, 0);
 
   for (uint32_t base = blockIdx.x * WG; base < n_pad; base += gridDim.x * WG) {
     const uint32_t i = base + threadIdx.x;
-    if constexpr (STDPRO) std_lane_prologue(i, n, n_pad, im, sa);  // (read back below by the same lane)
-    const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+    if constexpr (STDPRO) std_lane_prologue(i, n, SoAView{im, n_pad}, sa);  // (read back below by the same lane)
+    // (im indexed here, not through a view held by this body: see the view's header)
+    const uint32_t flags = im[(size_t)IM_FLAGS.off * n_pad + i];
     const bool valid = (i < n) && (flags & FLAG_VALID);
     ge q;
-    lane_q(q, im, n_pad, i, valid);
+    lane_q(q, SoACView{im, n_pad}, i, valid);
     const bool neg1 = (flags & FLAG_NEG1) != 0, neg2 = (flags & FLAG_NEG2) != 0;
 
     fe Zg;
@@ -714,7 +763,7 @@ __global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict_
 
     gej acc;
     bool inf;
-    q_chain<ILP>(acc, inf, im, n_pad, i, valid, qs, n_lanes, lane, park[8][threadIdx.x]);
+    q_chain<ILP>(acc, inf, SoACView{im, n_pad}, i, valid, qs, n_lanes, lane, park[8][threadIdx.x]);
 
     // hand B' = (X, Y, Z acc * Zg) on E_w to the finish kernel
     fe zt;
@@ -723,16 +772,13 @@ __global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict_
     fe_mul(zt, acc.z, Zg);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      im[(size_t)(IM_BX + k) * n_pad + i] = acc.x.v[k];
-      im[(size_t)(IM_BX + 8 + k) * n_pad + i] = acc.y.v[k];
-      im[(size_t)(IM_BX + 16 + k) * n_pad + i] = zt.v[k];
+      im[(size_t)(IM_BX.off + k) * n_pad + i] = acc.x.v[k];
+      im[(size_t)(IM_BY.off + k) * n_pad + i] = acc.y.v[k];
+      im[(size_t)(IM_BZ.off + k) * n_pad + i] = zt.v[k];
     }
-    im[(size_t)IM_FLAGS * n_pad + i] = flags | (inf ? FLAG_BINF : 0u);
+    im[(size_t)IM_FLAGS.off * n_pad + i] = flags | (inf ? FLAG_BINF : 0u);
   }
-  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    clk[2] = clock64();
-    clk[3] = wall_clock64();
-  }
+  clock_probe(clk, 2);
 }
 
 // ---------------------------------------------------------------------------
@@ -759,10 +805,11 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_qtable_kernel(const 
                                                                        uint32_t* __restrict__ qs) {
   const uint32_t s = blockIdx.x * WG + threadIdx.x;  // < cn: the grid is cn / WG blocks
   const uint32_t i = i0 + s;
-  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  const SoACView iv = {im, n_pad};
+  const uint32_t flags = iv.get(IM_FLAGS, i);
   const bool valid = (i < n) && (flags & FLAG_VALID);
   ge q;
-  lane_q(q, im, n_pad, i, valid);
+  lane_q(q, iv, i, valid);
   fe Zg;
   qtable_build(q, qs, cn, s, Zg);
   uint4* z = zg_ptr(qs, cn, s);
@@ -778,18 +825,16 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_chain_kernel(uint32_
   // they were spilled to scratch at 128 VGPRs; LDS is idle in this kernel
   __shared__ uint32_t signs[WG];
   // optional clock probe (hkv_profile_clock), as in hkv_ecmult_kernel
-  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    clk[0] = clock64();
-    clk[1] = wall_clock64();
-  }
+  clock_probe(clk, 0);
   const uint32_t s = blockIdx.x * WG + threadIdx.x;  // < cn: the grid is cn / WG blocks
   const uint32_t i = i0 + s;
-  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  // (im indexed here, not through a view held by this body: see the view's header)
+  const uint32_t flags = im[(size_t)IM_FLAGS.off * n_pad + i];
   const bool valid = (i < n) && (flags & FLAG_VALID);
   signs[threadIdx.x] = ((flags & FLAG_NEG1) ? 1u : 0u) | ((flags & FLAG_NEG2) ? 2u : 0u);
   gej acc;
   bool inf;
-  q_chain<false>(acc, inf, im, n_pad, i, valid, qs, cn, s, signs[threadIdx.x]);
+  q_chain<false>(acc, inf, SoACView{im, n_pad}, i, valid, qs, cn, s, signs[threadIdx.x]);
 
   // hand B' = (X, Y, Z acc * Zg) on E_w to the finish kernel
   fe Zg, zt;
@@ -802,15 +847,12 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_chain_kernel(uint32_
   fe_mul(zt, acc.z, Zg);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    im[(size_t)(IM_BX + k) * n_pad + i] = acc.x.v[k];
-    im[(size_t)(IM_BX + 8 + k) * n_pad + i] = acc.y.v[k];
-    im[(size_t)(IM_BX + 16 + k) * n_pad + i] = zt.v[k];
+    im[(size_t)(IM_BX.off + k) * n_pad + i] = acc.x.v[k];
+    im[(size_t)(IM_BY.off + k) * n_pad + i] = acc.y.v[k];
+    im[(size_t)(IM_BZ.off + k) * n_pad + i] = zt.v[k];
   }
-  im[(size_t)IM_FLAGS * n_pad + i] = flags | (inf ? FLAG_BINF : 0u);
-  if (clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    clk[2] = clock64();
-    clk[3] = wall_clock64();
-  }
+  im[(size_t)IM_FLAGS.off * n_pad + i] = flags | (inf ? FLAG_BINF : 0u);
+  clock_probe(clk, 2);
 }
 
 // ---------------------------------------------------------------------------
@@ -840,7 +882,6 @@ constexpr int PAIR_TPB = 256;  // (PAIR_SIGS: hkv_layout.h)
 // phase-stamp slots (clk[4 + slot]; include/hkv.h hkv_profile_phases)
 enum : int { STAMP_START = 0, STAMP_TABLE0, STAMP_P, STAMP_CHAIN0, STAMP_A, STAMP_JOIN, STAMP_SIG, STAMP_GSUM,
              STAMP_SQRT, STAMP_TABLE1, STAMP_CHAIN1, STAMP_COUNT };
-constexpr uint32_t AUXF_STDOK = 4u;  // STD: the script checks passed (aux AUX_FLAGS)
 // compress the even bits of a 64-bit lane mask into 32 bits (signature c = lanes 2c, 2c + 1)
 HKV_DEV uint32_t even_bits(uint64_t x) {
   x &= 0x5555555555555555ull;
@@ -956,8 +997,8 @@ HKV_DEV void pair_table(const fe& Q, int half, uint32_t odd, QLane& ql, HLane& h
 // The windows w_hi..w_lo (radix 16, top first) of one chain in pair form,
 // from infinity: P = X | Y, Z on the odd lane. half 0 takes k1's digits,
 // half 1 k2's; negh: the GLV half is negative.
-HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t* __restrict__ im, uint32_t n_pad,
-                        uint32_t i, bool valid, bool negh, int half, uint32_t odd, uint32_t ln, int w_hi, int w_lo) {
+HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, SoACView iv, uint32_t i, bool valid, bool negh,
+                        int half, uint32_t odd, uint32_t ln, int w_hi, int w_lo) {
   inf = true;
   fe_set_zero(P);
   fe_set_zero(Z);
@@ -968,7 +1009,7 @@ HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t
   const uint32_t dshift = half ? QDIG_BITS : 0u;
   const uint32_t negm = negh ? odd : 0u;  // the GLV half's sign on the odd (y) lane
   auto digit = [&](uint32_t w) { return (int)((w >> dshift) & QDIG_MASK) - QBIAS; };
-  uint32_t dw = valid ? im[(size_t)(IM_DIG + w_hi) * n_pad + i] : DIG_ZERO;
+  uint32_t dw = valid ? iv.get(IM_DIG, w_hi, i) : DIG_ZERO;
   bool dbl = false;  // the first window starts from infinity: no doublings
   if (w_hi == NWIN - 1 && w_hi > w_lo) {
     // The top two windows as one digit m = 2^QW d_top + d_next. The GLV
@@ -979,7 +1020,7 @@ HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t
     // pair of the wave made every pair run the next window's 4 doublings (5 %
     // of the halves reach 2^127: 80 % of the block kernel's groups). A wave
     // with any m outside [0, 16] runs the windows one by one.
-    const uint32_t dw2 = valid ? im[(size_t)(IM_DIG + w_hi - 1) * n_pad + i] : DIG_ZERO;
+    const uint32_t dw2 = valid ? iv.get(IM_DIG, w_hi - 1, i) : DIG_ZERO;
     const int m = (digit(dw) << QW) + digit(dw2);
     if (!__any(m < 0 || m > 2 * QBIAS)) {
       const int e1 = m < QBIAS ? m : QBIAS, e2 = m - e1;
@@ -996,7 +1037,7 @@ HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t
       }
       w_hi -= 2;
       dbl = true;
-      dw = (w_hi >= w_lo && valid) ? im[(size_t)(IM_DIG + w_hi) * n_pad + i] : DIG_ZERO;
+      dw = (w_hi >= w_lo && valid) ? iv.get(IM_DIG, w_hi, i) : DIG_ZERO;
     }
   }
 #pragma unroll 1
@@ -1004,7 +1045,7 @@ HKV_DEV void pair_chain(fe& P, fe& Z, bool& inf, const QLane& ql, const uint32_t
     const int dg = digit(dw);
     const int mg = dg < 0 ? -dg : dg;
     const int ie = mg ? mg - 1 : 0;
-    const uint32_t dw_next = (win > w_lo && valid) ? im[(size_t)(IM_DIG + win - 1) * n_pad + i] : DIG_ZERO;
+    const uint32_t dw_next = (win > w_lo && valid) ? iv.get(IM_DIG, win - 1, i) : DIG_ZERO;
     if (dbl) {
 #pragma unroll 1
       for (int d = 0; d < QW; ++d) {
@@ -1090,7 +1131,7 @@ HKV_DEV void key_point(uint32_t i, uint32_t n, const uint32_t* __restrict__ recs
 // The signature wave, first half (lanes with on): range and high-S policy,
 // s^-1, u2, the GLV split and Booth digits, r and the flags into im.
 template <bool STD>
-HKV_DEV void sig_wave_parse(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint32_t mode, uint32_t* __restrict__ im,
+HKV_DEV void sig_wave_parse(uint32_t i, bool on, uint32_t n, uint32_t mode, SoAView iv,
                             const uint32_t* __restrict__ recs, const StdArgs& sa, StdIn& x, sc& m, sc& sinv,
                             bool& use, uint32_t& flags, TxView v = {nullptr, nullptr}) {
   flags = 0;
@@ -1112,13 +1153,13 @@ HKV_DEV void sig_wave_parse(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uin
     rec_be256(s.v, w, 64);
     rec_be256(m.v, w, 0);
   }
-  sig_lane_q(r, s, mode, im, n_pad, i, ok, glv_ok, n1, n2, sinv);
+  sig_lane_q(r, s, mode, iv, i, ok, glv_ok, n1, n2, sinv);
   use = ok && glv_ok;
   fe kx, kwv;
   uint32_t pflags = 0;
   const bool pk = pubkey_parse_rec_w(kw, kx, kwv, pflags) && i < n;
   flags = split_flags(ok, (pk ? 1u : 0u) | pflags, glv_ok, n1, n2);
-  im[(size_t)IM_FLAGS * n_pad + i] = flags;
+  iv.put(IM_FLAGS, i, flags);
 }
 // 1e. Mid-size standard-input batches (at most 2 waves per SIMD; the
 //     overlapped path of hkv_api.cpp enqueue_std_chunk): std_parse
@@ -1129,7 +1170,7 @@ HKV_DEV void sig_wave_parse(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uin
 //     (hkv_std_input_kernel, on a second stream from the start) writes it
 //     whole, and the finish kernel (LATE) redoes u1 from it after the join; s^-1
 //     stays in IM_C for that.
-HKV_DEV void std_lane_prologue(uint32_t i, uint32_t n, uint32_t n_pad, uint32_t* __restrict__ im, const StdArgs& sa) {
+HKV_DEV void std_lane_prologue(uint32_t i, uint32_t n, SoAView iv, const StdArgs& sa) {
   bool glv_ok, n1, n2;
   uint32_t kw[REC_WORDS];
   StdIn x = {};
@@ -1138,17 +1179,17 @@ HKV_DEV void std_lane_prologue(uint32_t i, uint32_t n, uint32_t n_pad, uint32_t*
 #pragma unroll
   for (int k = 0; k < 8; ++k) { r.v[k] = x.r[k]; s.v[k] = x.s[k]; m.v[k] = 0; }
   bool ok = i < n && x.ok;
-  sig_lane_q(r, s, HKV_MODE_HASKOIN, im, n_pad, i, ok, glv_ok, n1, n2, sinv);
-  sig_lane_g(m, sinv, ok && glv_ok, im, n_pad, i);
+  sig_lane_q(r, s, HKV_MODE_HASKOIN, iv, i, ok, glv_ok, n1, n2, sinv);
+  sig_lane_g(m, sinv, ok && glv_ok, iv, i);
   fe kx, kwv;
   uint32_t pflags = 0;
   const bool pk = pubkey_parse_rec_w(kw, kx, kwv, pflags) && i < n;
-  im[(size_t)IM_FLAGS * n_pad + i] = split_flags(ok, (pk ? 1u : 0u) | pflags, glv_ok, n1, n2);
+  iv.put(IM_FLAGS, i, split_flags(ok, (pk ? 1u : 0u) | pflags, glv_ok, n1, n2));
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    im[(size_t)(IM_QX + k) * n_pad + i] = kx.v[k];
-    im[(size_t)(IM_W + k) * n_pad + i] = kwv.v[k];
-    im[(size_t)(IM_C + k) * n_pad + i] = sinv.v[k];
+    iv.put(IM_QX, k, i, kx.v[k]);
+    iv.put(IM_W, k, i, kwv.v[k]);
+    iv.put(IM_C, k, i, sinv.v[k]);
   }
 }
 
@@ -1160,10 +1201,9 @@ HKV_DEV void std_lane_prologue(uint32_t i, uint32_t n, uint32_t n_pad, uint32_t*
 // 0: each input's lane computes them in turn; -1: another wave has put them
 // in r32 + 8 (the block kernel's wave 0, blk_tx_hashes).
 template <bool STD, int SPREAD = 0>
-HKV_DEV void sig_wave_gsum(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint32_t* __restrict__ im,
-                           const uint32_t* __restrict__ gtab, uint32_t* __restrict__ aux, uint32_t* __restrict__ recs,
-                           const StdArgs& sa, uint32_t* shabuf, StdIn& x, sc m, const sc& sinv, bool use,
-                           uint32_t flags) {
+HKV_DEV void sig_wave_gsum(uint32_t i, bool on, uint32_t n, SoAView iv, const uint32_t* __restrict__ gtab, SoAView av,
+                           uint32_t* __restrict__ recs, const StdArgs& sa, uint32_t* shabuf, StdIn& x, sc m,
+                           const sc& sinv, bool use, uint32_t flags) {
   uint32_t stdok = 0;
   if constexpr (STD) {
     uint32_t* r32 = recs + (size_t)(on && i < n ? i : 0) * REC_WORDS;
@@ -1185,22 +1225,22 @@ HKV_DEV void sig_wave_gsum(uint32_t i, bool on, uint32_t n, uint32_t n_pad, uint
     }
   }
   if (!on) return;
-  sig_lane_g(m, sinv, use, im, n_pad, i);
+  sig_lane_g(m, sinv, use, iv, i);
   gej A;
   bool ainf;
-  gsum_lane(im, n_pad, gtab, i, (flags & FLAG_VALID) != 0, A, ainf);
+  gsum_lane(iv, gtab, i, (flags & FLAG_VALID) != 0, A, ainf);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    aux[(size_t)(AUX_AX + k) * n_pad + i] = A.x.v[k];
-    aux[(size_t)(AUX_AX + 8 + k) * n_pad + i] = A.y.v[k];
-    aux[(size_t)(AUX_AX + 16 + k) * n_pad + i] = A.z.v[k];
+    av.put(AUX_AX, k, i, A.x.v[k]);
+    av.put(AUX_AY, k, i, A.y.v[k]);
+    av.put(AUX_AZ, k, i, A.z.v[k]);
   }
-  aux[(size_t)AUX_FLAGS * n_pad + i] = (ainf ? AUXF_AINF : 0u) | stdok;
+  av.put(AUX_FLAGS, i, (ainf ? AUXF_AINF : 0u) | stdok);
 }
 // The key's y0 = sqrt(w) with the key's y parity, and whether w is a square
 template <bool STD>
-HKV_DEV void sqrt_lane(uint32_t i, uint32_t n, uint32_t n_pad, const uint32_t* __restrict__ recs, const StdArgs& sa,
-                       uint32_t* __restrict__ aux, TxView v = {nullptr, nullptr}) {
+HKV_DEV void sqrt_lane(uint32_t i, uint32_t n, const uint32_t* __restrict__ recs, const StdArgs& sa, SoAView av,
+                       TxView v = {nullptr, nullptr}) {
   uint32_t kw[REC_WORDS];
   StdIn xs = {};
   key_words_of<STD>(i, n, recs, sa, kw, xs, v, true);
@@ -1215,22 +1255,22 @@ HKV_DEV void sqrt_lane(uint32_t i, uint32_t n, uint32_t n_pad, const uint32_t* _
   fe_normalize(ny);
   if ((y0.v[0] & 1u) != ((pflags & FLAG_YODD) ? 1u : 0u)) y0 = ny;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) aux[(size_t)(AUX_Y0 + k) * n_pad + i] = y0.v[k];
-  aux[(size_t)AUX_SQ * n_pad + i] = is_sq ? AUXF_SQ : 0u;
+  for (int k = 0; k < 8; ++k) av.put(AUX_Y0, k, i, y0.v[k]);
+  av.put(AUX_SQ, i, is_sq ? AUXF_SQ : 0u);
 }
 // A, y0, the join flags and r of signature i (aux / im)
-HKV_DEV void join_inputs(const uint32_t* __restrict__ im, const uint32_t* __restrict__ aux, uint32_t n_pad,
-                         uint32_t i, gej& A, fe& y0, uint32_t r[8], uint32_t& af, bool& is_sq) {
+HKV_DEV void join_inputs(SoACView iv, SoACView av, uint32_t i, gej& A, fe& y0, uint32_t r[8], uint32_t& af,
+                         bool& is_sq) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    A.x.v[k] = aux[(size_t)(AUX_AX + k) * n_pad + i];
-    A.y.v[k] = aux[(size_t)(AUX_AX + 8 + k) * n_pad + i];
-    A.z.v[k] = aux[(size_t)(AUX_AX + 16 + k) * n_pad + i];
-    y0.v[k] = aux[(size_t)(AUX_Y0 + k) * n_pad + i];
-    r[k] = im[(size_t)(IM_R + k) * n_pad + i];
+    A.x.v[k] = av.get(AUX_AX, k, i);
+    A.y.v[k] = av.get(AUX_AY, k, i);
+    A.z.v[k] = av.get(AUX_AZ, k, i);
+    y0.v[k] = av.get(AUX_Y0, k, i);
+    r[k] = iv.get(IM_R, k, i);
   }
-  af = aux[(size_t)AUX_FLAGS * n_pad + i];
-  is_sq = aux[(size_t)AUX_SQ * n_pad + i] != 0;
+  af = av.get(AUX_FLAGS, i);
+  is_sq = av.get(AUX_SQ, i) != 0;
 }
 
 // One group of PAIR_SIGS signatures (records base .. base + 31) on the
@@ -1250,6 +1290,9 @@ HKV_DEV void pair_group(uint32_t base, uint32_t* __restrict__ im, uint32_t n, ui
   auto mark = [&](int slot) {
     if (stamp) clk[4 + slot] = wall_clock64();
   };
+  // (im and aux stay raw pointers in this signature on purpose: the multisig
+  // tail hands over slot-relative ones, and the views are built from those)
+  const SoAView iv = {im, n_pad}, av = {aux, n_pad};
   if (wv == 2) {
     // ---- the signature: u2 half (lanes 0-31), then the u1 half and A = u1 G ----
     const uint32_t i = base + ln;
@@ -1258,11 +1301,11 @@ HKV_DEV void pair_group(uint32_t base, uint32_t* __restrict__ im, uint32_t n, ui
     bool use;
     sc sinv, m;
     StdIn x = {};
-    sig_wave_parse<STD>(i, on, n, n_pad, mode, im, recs, sa, x, m, sinv, use, flags);
+    sig_wave_parse<STD>(i, on, n, mode, iv, recs, sa, x, m, sinv, use, flags);
     __threadfence_block();
     mark(STAMP_SIG);
     __syncthreads();  // barrier P
-    sig_wave_gsum<STD>(i, on, n, n_pad, im, gtab, aux, recs, sa, shabuf, x, m, sinv, use, flags);
+    sig_wave_gsum<STD>(i, on, n, iv, gtab, av, recs, sa, shabuf, x, m, sinv, use, flags);
     __threadfence_block();
     mark(STAMP_GSUM);
     __syncthreads();  // barrier A
@@ -1272,7 +1315,7 @@ HKV_DEV void pair_group(uint32_t base, uint32_t* __restrict__ im, uint32_t n, ui
   if (wv == 3) {
     // ---- the key's y0 = sqrt(w) with the key's y parity (lanes 0-31) ----
     __syncthreads();  // barrier P (nothing to wait for: the key bytes are input)
-    if (ln < PAIR_SIGS) sqrt_lane<STD>(base + ln, n, n_pad, recs, sa, aux);
+    if (ln < PAIR_SIGS) sqrt_lane<STD>(base + ln, n, recs, sa, av);
     __threadfence_block();
     mark(STAMP_SQRT);
     __syncthreads();  // barrier A
@@ -1293,14 +1336,14 @@ HKV_DEV void pair_group(uint32_t base, uint32_t* __restrict__ im, uint32_t n, ui
   mark(half ? STAMP_TABLE1 : STAMP_TABLE0);
   __syncthreads();  // barrier P: the signature wave's digits, r and flags are in im
   if (half == 0) mark(STAMP_P);
-  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  const uint32_t flags = iv.get(IM_FLAGS, i);
   const bool valid = (i < n) && (flags & FLAG_VALID);
   const bool negh = (flags & (half ? FLAG_NEG2 : FLAG_NEG1)) != 0;
 
   // ---- the chain: 33 radix-16 windows, pair form ----
   fe P, Z;
   bool inf;
-  pair_chain(P, Z, inf, qlds[half], im, n_pad, i, valid, negh, half, odd, ln, NWIN - 1, 0);
+  pair_chain(P, Z, inf, qlds[half], iv, i, valid, negh, half, odd, ln, NWIN - 1, 0);
 
   mark(half ? STAMP_CHAIN1 : STAMP_CHAIN0);
   // ---- join: half 1's sum to half 0 through LDS ----
@@ -1323,7 +1366,7 @@ HKV_DEV void pair_group(uint32_t base, uint32_t* __restrict__ im, uint32_t n, ui
     fe y0;
     uint32_t r[8], af;
     bool is_sq;
-    join_inputs(im, aux, n_pad, i, A, y0, r, af, is_sq);
+    join_inputs(iv, av, i, A, y0, r, af, is_sq);
     // B = phi^-1(B') = (X, Y, Z Zg y0) on E, R = A + B exactly, x compare
     gej bb;
     bb.x = acc.x;
@@ -1607,6 +1650,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
   auto mark = [&](int slot) {
     if (stamp) clk[4 + slot] = wall_clock64();
   };
+  const SoAView iv = {im, n_pad}, av = {aux, n_pad};
   if (threadIdx.x < BF_COUNT) bflag[threadIdx.x] = 0;
   if (clk != nullptr && threadIdx.x == 0 && blockIdx.x < 4096) clk[16 + 2 * blockIdx.x] = wall_clock64();
   __syncthreads();
@@ -1626,13 +1670,12 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
       bool use;
       sc sinv, m;
       StdIn x = {};
-      sig_wave_parse<STD>(i, on, n, n_pad, mode, im, recs, sa, x, m, sinv, use, flags,
+      sig_wave_parse<STD>(i, on, n, mode, iv, recs, sa, x, m, sinv, use, flags,
                           blk_view<STD>(tcache, ln & (BLK_SIGS - 1)));
       blk_post(&bflag[BF_SIG], seq);
       mark(STAMP_SIG);
       if constexpr (STD) blk_wait(&bflag[BF_H], seq);  // the BIP143 per-tx hashes (wave 0)
-      sig_wave_gsum<STD, (STD ? -1 : BLK_SIGS)>(i, on, n, n_pad, im, gtab, aux, recs, sa, shabuf, x, m, sinv, use,
-                                                flags);
+      sig_wave_gsum<STD, (STD ? -1 : BLK_SIGS)>(i, on, n, iv, gtab, av, recs, sa, shabuf, x, m, sinv, use, flags);
       blk_post(&bflag[BF_A], seq);
       mark(STAMP_GSUM);
       // STD: the multisig scan of the group's inputs (off every critical path)
@@ -1709,7 +1752,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
       pair_table(P, half, odd, qlds[1], hlds[1], ln, Zg);
       mark(STAMP_TABLE1);
     } else {
-      if (ln < BLK_SIGS) sqrt_lane<STD>(base + ln, n, n_pad, recs, sa, aux, blk_view<STD>(tcache, ln));
+      if (ln < BLK_SIGS) sqrt_lane<STD>(base + ln, n, recs, sa, av, blk_view<STD>(tcache, ln));
       blk_post(&bflag[BF_Y], seq);
       mark(STAMP_SQRT);
       blk_wait(&bflag[BF_Q], seq);  // Q1 from wave 1
@@ -1722,7 +1765,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
     }
     blk_wait(&bflag[BF_SIG], seq);  // the digits, r and flags are in im
     if (wv == 0) mark(STAMP_P);
-    const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+    const uint32_t flags = iv.get(IM_FLAGS, i);
     const bool valid = (i < n) && (flags & FLAG_VALID);
     const bool negh = (flags & (half ? FLAG_NEG2 : FLAG_NEG1)) != 0;
     const int w_hi = wv == 0 ? k1 - 1 : (wv == 1 ? NWIN - 1 : BLK_K2 - 1);
@@ -1730,7 +1773,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
     fe zs;  // the segment's isomorphic scale (formed before the chain: off the join's path)
     fe_mul(zs, Zg, zb);
     bool inf;
-    pair_chain(P, Z, inf, qlds[slot], im, n_pad, i, valid, negh, half, odd, ln, w_hi, w_lo);
+    pair_chain(P, Z, inf, qlds[slot], iv, i, valid, negh, half, odd, ln, w_hi, w_lo);
     mark(wv == 0 ? STAMP_CHAIN0 : (wv == 1 ? STAMP_CHAIN1 : STAMP_CHAIN_MID));
     fe Zs;
     halves_sum(xch[slot], c, half, odd, P, Z, inf, Zs);  // S = P | Zs on E_w at scale Zg * zb
@@ -1744,7 +1787,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
         fe y0, PA;
         uint32_t r[8], af;
         bool is_sq;
-        join_inputs(im, aux, n_pad, i, A, y0, r, af, is_sq);
+        join_inputs(iv, av, i, A, y0, r, af, is_sq);
         bool tinf = (af & AUXF_AINF) != 0;
         fe_sel(PA, A.x, A.y, odd);
         add_segment(PA, A.z, tinf, P, Zs, inf, zs, y0, odd);
@@ -1759,7 +1802,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
       if (half == 0) {
         fe y0, zt;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) y0.v[k] = aux[(size_t)(AUX_Y0 + k) * n_pad + i];
+        for (int k = 0; k < 8; ++k) y0.v[k] = av.get(AUX_Y0, k, i);
         fe_mul(zt, Zs, zs);
         fe_mul(zbs, zt, y0);
       }
@@ -1784,7 +1827,7 @@ __global__ void __launch_bounds__(BLK_TPB, 1) hkv_block_kernel(uint32_t* __restr
       uint32_t r[8], af;
       bool is_sq;
       if (half == 0) {
-        join_inputs(im, aux, n_pad, i, A, y0, r, af, is_sq);
+        join_inputs(iv, av, i, A, y0, r, af, is_sq);
         fe zt;
         fe_mul(zt, Zs, zs);
         fe_mul(zb, zt, y0);
@@ -1888,24 +1931,23 @@ HKV_DEV void gtab_entry(const uint32_t* __restrict__ gtab, int t, uint32_t gd, f
 // per-window tables (no doublings); ILP: the paired-product addition (mid-size
 // launches, at most 2 waves per SIMD)
 template <bool ILP>
-HKV_DEV void gsum_lane(const uint32_t* __restrict__ im, uint32_t n_pad, const uint32_t* __restrict__ gtab, uint32_t i,
-                       bool valid, gej& A, bool& ainf) {
+HKV_DEV void gsum_lane(SoACView iv, const uint32_t* __restrict__ gtab, uint32_t i, bool valid, gej& A, bool& ainf) {
   // ---- A = u1 * G: one affine addition per window, table t = 2j + h holds
   // multiples of 2^(GTAB_W j + 128 h) G; the next entry is loaded before
   // the current addition
   // (window 0 starts the sum: A = its entry, affine, without an addition)
-  uint32_t gd = valid ? im[(size_t)IM_GDIG * n_pad + i] : 0u;
+  uint32_t gd = valid ? iv.get(IM_GDIG, i) : 0u;
   fe tx, ty;
   gtab_entry(gtab, 0, gd, tx, ty);
   fe_cneg(A.y, ty, (gd & GD_NEG) != 0);
   A.x = tx;
   fe_set_u32(A.z, 1);
   ainf = (gd & GD_MAG) == 0;
-  gd = valid ? im[(size_t)(IM_GDIG + 1) * n_pad + i] : 0u;
+  gd = valid ? iv.get(IM_GDIG, 1, i) : 0u;
   gtab_entry(gtab, 1, gd, tx, ty);
 #pragma unroll 1
   for (int t = 1; t < 2 * GWIN; ++t) {
-    const uint32_t gdn = (t + 1 < 2 * GWIN && valid) ? im[(size_t)(IM_GDIG + t + 1) * n_pad + i] : 0u;
+    const uint32_t gdn = (t + 1 < 2 * GWIN && valid) ? iv.get(IM_GDIG, t + 1, i) : 0u;
     fe nx, nyy;
     if (t + 1 < 2 * GWIN) gtab_entry(gtab, t + 1, gdn, nx, nyy);
     const bool take = (gd & GD_MAG) != 0;
@@ -1926,18 +1968,19 @@ HKV_DEV void gsum_lane(const uint32_t* __restrict__ im, uint32_t n_pad, const ui
 // LATE (large standard-input batches): the lane's G digits and validity come
 // from its final record first (late_u1_lane; its own digit words, read back
 // below by the same lane)
+// (im, n_pad and a view built at each use: see the view's header)
 template <bool ILP, bool LATE>
 HKV_DEV void finish_lane(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad, const uint32_t* __restrict__ gtab,
                          uint32_t* __restrict__ rare_ctr, uint32_t i, uint32_t flags,
                          const uint32_t* __restrict__ recs) {
   if constexpr (LATE) {
-    if (i < n) flags = late_u1_lane(recs, i, n_pad, im, flags);
+    if (i < n) flags = late_u1_lane(recs, i, SoAView{im, n_pad}, flags);
   }
   const bool valid = (i < n) && (flags & FLAG_VALID);
 
   gej A;
   bool ainf;
-  gsum_lane<ILP>(im, n_pad, gtab, i, valid, A, ainf);
+  gsum_lane<ILP>(SoAView{im, n_pad}, gtab, i, valid, A, ainf);
 
   // ---- B' from the ecmult kernel, w, r (not hoisted above the loop: it
   // would hold 56 more VGPRs through every addition)
@@ -1947,11 +1990,11 @@ HKV_DEV void finish_lane(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad, 
   uint32_t r[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    B.x.v[k] = im[(size_t)(IM_BX + k) * n_pad + i];
-    B.y.v[k] = im[(size_t)(IM_BX + 8 + k) * n_pad + i];
-    B.z.v[k] = im[(size_t)(IM_BX + 16 + k) * n_pad + i];
-    w.v[k] = im[(size_t)(IM_W + k) * n_pad + i];
-    r[k] = im[(size_t)(IM_R + k) * n_pad + i];
+    B.x.v[k] = SoAView{im, n_pad}.get(IM_BX, k, i);
+    B.y.v[k] = SoAView{im, n_pad}.get(IM_BY, k, i);
+    B.z.v[k] = SoAView{im, n_pad}.get(IM_BZ, k, i);
+    w.v[k] = SoAView{im, n_pad}.get(IM_W, k, i);
+    r[k] = SoAView{im, n_pad}.get(IM_R, k, i);
   }
   const bool binf = (flags & FLAG_BINF) != 0;
 
@@ -2039,25 +2082,25 @@ HKV_DEV void finish_lane(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad, 
                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)rmask, 0u));
     // (at most n_pad rare lanes per batch; the clamp keeps a stale count from
     // a failed earlier call inside the row)
-    if (rare && base + rank < n_pad) im[(size_t)IM_RARE_LIST * n_pad + base + rank] = i;
+    if (rare && base + rank < n_pad) SoAView{im, n_pad}.put(IM_RARE_LIST, (size_t)base + rank, i);
   }
   if (rare) {
     fo |= FLAG_RARE | (ainf ? FLAG_AINF : 0u);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      im[(size_t)(IM_AX + k) * n_pad + i] = A.x.v[k];
-      im[(size_t)(IM_AY + k) * n_pad + i] = A.y.v[k];
-      im[(size_t)(IM_AY + 8 + k) * n_pad + i] = A.z.v[k];
+      SoAView{im, n_pad}.put(IM_AX, k, i, A.x.v[k]);
+      SoAView{im, n_pad}.put(IM_AY, k, i, A.y.v[k]);
+      SoAView{im, n_pad}.put(IM_AZ, k, i, A.z.v[k]);
     }
   } else {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      im[(size_t)(IM_NUM + k) * n_pad + i] = num.v[k];
-      im[(size_t)(IM_NUM + 8 + k) * n_pad + i] = numn.v[k];
-      im[(size_t)(IM_DEN + k) * n_pad + i] = den.v[k];
+      SoAView{im, n_pad}.put(IM_NUM, k, i, num.v[k]);
+      SoAView{im, n_pad}.put(IM_NUMN, k, i, numn.v[k]);
+      SoAView{im, n_pad}.put(IM_DEN, k, i, den.v[k]);
     }
   }
-  im[(size_t)IM_FLAGS * n_pad + i] = fo;
+  SoAView{im, n_pad}.put(IM_FLAGS, i, fo);
 }
 
 template <bool ILP, bool LATE>
@@ -2068,7 +2111,7 @@ __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_FINISH_WAVES) hkv_finish_ker
                                                                                  const uint32_t* __restrict__ recs) {
   const uint32_t i = blockIdx.x * WG + threadIdx.x;
   if (i >= n_pad) return;
-  finish_lane<ILP, LATE>(im, n, n_pad, gtab, rare_ctr, i, im[(size_t)IM_FLAGS * n_pad + i], recs);
+  finish_lane<ILP, LATE>(im, n, n_pad, gtab, rare_ctr, i, SoAView{im, n_pad}.get(IM_FLAGS, i), recs);
 }
 
 // the exact slow path for the finish kernel's rare lanes: y0 = sqrt(w) of
@@ -2079,22 +2122,23 @@ __global__ void __launch_bounds__(WG) hkv_rare_kernel(uint32_t* __restrict__ im,
                                                       const uint32_t* __restrict__ rare_ctr) {
   const uint32_t k = blockIdx.x * WG + threadIdx.x;
   if (k >= min(*rare_ctr, n_pad)) return;
-  const uint32_t i = im[(size_t)IM_RARE_LIST * n_pad + k];
-  const uint32_t flags = im[(size_t)IM_FLAGS * n_pad + i];
+  const SoAView iv = {im, n_pad};
+  const uint32_t i = iv.get(IM_RARE_LIST, k);
+  const uint32_t flags = iv.get(IM_FLAGS, i);
   const bool rare = true;
   gej A, B;
   fe w;
   uint32_t r[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    A.x.v[k] = im[(size_t)(IM_AX + k) * n_pad + i];
-    A.y.v[k] = im[(size_t)(IM_AY + k) * n_pad + i];
-    A.z.v[k] = im[(size_t)(IM_AY + 8 + k) * n_pad + i];
-    B.x.v[k] = im[(size_t)(IM_BX + k) * n_pad + i];
-    B.y.v[k] = im[(size_t)(IM_BX + 8 + k) * n_pad + i];
-    B.z.v[k] = im[(size_t)(IM_BX + 16 + k) * n_pad + i];
-    w.v[k] = im[(size_t)(IM_W + k) * n_pad + i];
-    r[k] = im[(size_t)(IM_R + k) * n_pad + i];
+    A.x.v[k] = iv.get(IM_AX, k, i);
+    A.y.v[k] = iv.get(IM_AY, k, i);
+    A.z.v[k] = iv.get(IM_AZ, k, i);
+    B.x.v[k] = iv.get(IM_BX, k, i);
+    B.y.v[k] = iv.get(IM_BY, k, i);
+    B.z.v[k] = iv.get(IM_BZ, k, i);
+    w.v[k] = iv.get(IM_W, k, i);
+    r[k] = iv.get(IM_R, k, i);
   }
   fe y0, y2, ny;
   fe_sqrt_cand(y0, w);
@@ -2109,7 +2153,7 @@ __global__ void __launch_bounds__(WG) hkv_rare_kernel(uint32_t* __restrict__ im,
   bool rinf = (flags & FLAG_AINF) != 0;
   gej_add_var(A, rinf, b, (flags & FLAG_BINF) != 0);
   const bool acc_ok = is_sq && !rinf && x_matches_r(A.x, A.z, r);
-  if (rare) im[(size_t)IM_FLAGS * n_pad + i] = flags | FLAG_DECIDED | (acc_ok ? FLAG_ACCEPT : 0u);
+  if (rare) iv.put(IM_FLAGS, i, flags | FLAG_DECIDED | (acc_ok ? FLAG_ACCEPT : 0u));
 }
 
 // verdicts: den^-1 by Montgomery's trick over VERDICT_BATCH signatures per lane
@@ -2118,6 +2162,7 @@ __global__ void __launch_bounds__(WG) hkv_rare_kernel(uint32_t* __restrict__ im,
 __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t stride,
                                                           uint32_t* __restrict__ bits, uint32_t n_words,
                                                           uint32_t* __restrict__ rare_ctr) {
+  // (im through ld8 / st8 and indexed here: see the view's header)
   const uint32_t t = blockIdx.x * WG + threadIdx.x;
   if (t == 0) *rare_ctr = 0;  // re-arm for the next batch (the rare kernel has read it)
   // one wave per SIMD at 1M: the loops are load-latency bound, so each
@@ -2127,8 +2172,8 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
   int kn = 0;
   {
     fe d;
-    im_load8(im, n_pad, IM_DEN, t, d.v);  // t < stride <= n_pad
-    uint32_t fl = im[(size_t)IM_FLAGS * n_pad + t];
+    SoACView::ld8(im, n_pad, IM_DEN.off, t, d.v);  // t < stride <= n_pad
+    uint32_t fl = im[(size_t)IM_FLAGS.off * n_pad + t];
 #pragma unroll 1
     for (int k = 0; k < VERDICT_BATCH; ++k) {
       const uint32_t i = t + (uint32_t)k * stride;
@@ -2138,12 +2183,12 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
       fe dn;
       uint32_t fn = 0;
       if (k + 1 < VERDICT_BATCH && inext < n_pad) {
-        im_load8(im, n_pad, IM_DEN, inext, dn.v);
-        fn = im[(size_t)IM_FLAGS * n_pad + inext];
+        SoACView::ld8(im, n_pad, IM_DEN.off, inext, dn.v);
+        fn = im[(size_t)IM_FLAGS.off * n_pad + inext];
       }
       if (fl & FLAG_DECIDED) fe_set_u32(d, 1);
       fe_mul(c, c, d);
-      im_store8(im, n_pad, IM_C, i, c.v);
+      SoAView::st8(im, n_pad, IM_C.off, i, c.v);
       d = dn;
       fl = fn;
     }
@@ -2158,12 +2203,12 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
   };
   auto load_ops = [&](Ops& o, int k) {
     const uint32_t i = t + (uint32_t)k * stride;
-    o.f = im[(size_t)IM_FLAGS * n_pad + i];
-    if (k > 0) im_load8(im, n_pad, IM_C, i - stride, o.prev.v);
-    im_load8(im, n_pad, IM_DEN, i, o.d.v);
-    im_load8(im, n_pad, IM_NUM, i, o.num.v);
-    im_load8(im, n_pad, IM_W, i, o.w.v);
-    im_load8(im, n_pad, IM_R, i, o.r);
+    o.f = im[(size_t)IM_FLAGS.off * n_pad + i];
+    if (k > 0) SoACView::ld8(im, n_pad, IM_C.off, i - stride, o.prev.v);
+    SoACView::ld8(im, n_pad, IM_DEN.off, i, o.d.v);
+    SoACView::ld8(im, n_pad, IM_NUM.off, i, o.num.v);
+    SoACView::ld8(im, n_pad, IM_W.off, i, o.w.v);
+    SoACView::ld8(im, n_pad, IM_R.off, i, o.r);
   };
   Ops cur;
   if (kn > 0) load_ops(cur, kn - 1);
@@ -2190,7 +2235,7 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
       const bool small_r = u256_lt(cur.r, PMN);
       if (__any(!ok && small_r)) {
         fe numn;
-        im_load8(im, n_pad, IM_NUM + 8, i, numn.v);
+        SoACView::ld8(im, n_pad, IM_NUMN.off, i, numn.v);
         fe_mul(yc, numn, dinv);
         fe_normalize(yc);
         fe_sqr(y2, yc);

@@ -8,23 +8,6 @@ namespace hkv {
 constexpr int REC_SIZE = 168;
 constexpr int REC_WORDS = REC_SIZE / 4;
 
-// Prologue -> ecmult intermediate, SoA: word w of signature i at [w * n_pad + i].
-enum : int {
-  IM_FLAGS = 0,   // bit0 valid, bit1 k1 negative, bit2 k2 negative, bit3 glv overflow
-  IM_QX = 1,      // 8 limbs, affine pubkey x (normalised)
-  IM_QY = 9,      // 8 limbs, affine pubkey y (normalised)
-  IM_K1 = 17,     // 5 limbs, |k1| < 2^129   (u2 = k1 + k2*lambda)
-  IM_K2 = 22,     // 5 limbs, |k2| < 2^129
-  IM_U1L = 27,    // 4 limbs, u1 bits 0..127
-  IM_U1H = 31,    // 4 limbs, u1 bits 128..255
-  IM_R = 35,      // 8 limbs, r (< n)
-  IM_C = 43,      // 8 limbs, batch-inversion prefix product, then s^-1
-  IM_DIG = 51,    // NWIN (<= 33) words: window w's radix-2^QW Booth digits of k1, k2
-  IM_GDIG = 84,   // 2 x GWIN words: radix-2^GTAB_W Booth digits of u1_lo, u1_hi
-  // between the parse and scalar kernels: s (normalised) and m = msg mod n
-  IM_S = IM_K1,   // 8 limbs over K1|K2 (10 words)
-  IM_M = IM_U1L,  // 8 limbs over U1L|U1H
-};
 // Q digit word of window w (w = 0..NWIN-1, bit position QW*w): biased Booth
 //   digits, bits 0..QW d1 + QBIAS (k1, radix 2^QW, -QBIAS..QBIAS), bits
 //   QW+1..2QW+1 d2 + QBIAS (k2)
@@ -46,14 +29,12 @@ static_assert(QW == 4 || QW == 5, "radix-16 or radix-32 Q windows");
 constexpr int GTAB_W = HKV_GTAB_W;            // Booth radix of the fixed-base tables
 static_assert(GTAB_W % QW == 0 && GTAB_W >= 8 && GTAB_W <= 28, "G windows sit on Q window boundaries");
 constexpr int NWIN = (130 + QW - 1) / QW;        // 33 / 26: |k| < 2^129 plus the Booth carry
-static_assert(IM_DIG + NWIN <= IM_GDIG, "digit words fit");
 constexpr int QBIAS = 1 << (QW - 1);             // digit range -QBIAS..QBIAS
 constexpr int QDIG_BITS = QW + 1;                // width of a biased digit in the digit word
 constexpr uint32_t QDIG_MASK = (1u << QDIG_BITS) - 1u;
 constexpr int GWIN = (128 + GTAB_W) / GTAB_W;  // covers 129 bits with the Booth carry
 constexpr int GSTEP = GTAB_W / QW;             // Q windows per G window
 constexpr uint32_t GD_MAG = (1u << GTAB_W) - 1u, GD_NEG = 1u << GTAB_W;
-constexpr int IM_WORDS = IM_GDIG + 2 * GWIN;
 constexpr uint32_t DIG_ZERO = (uint32_t)QBIAS | ((uint32_t)QBIAS << QDIG_BITS);
 
 // signatures per thread in the scalar kernel (one s^-1 per BATCH_INV via
@@ -72,10 +53,9 @@ constexpr int VERDICT_BATCH = HKV_VERDICT_BATCH;
 // the pair-lane split kernel takes 32 on 4 waves, the block kernel 16
 constexpr int PAIR_SIGS = 32;
 constexpr int BLK_SIGS = 16;
-constexpr uint32_t FLAG_VALID = 1u, FLAG_NEG1 = 2u, FLAG_NEG2 = 4u, FLAG_GLV_OVF = 8u;
 
 // y-free verification (every launch shape; hkv_kernels.hip §2b): the
-// prologue stores w = x^3 + 7 over IM_QY instead of solving y = sqrt(w);
+// prologue stores w = x^3 + 7 (IM_W) instead of solving y = sqrt(w);
 // ecmult runs u2 * Q' on E_w : y^2 = x^3 + 7 w^3 with Q' = (x w, w^2) and
 // leaves B' = (X, Y, Z) over the Q-digit words; the finish kernel adds the
 // u1 * G sum from per-window tables and reduces "x(u1 G + u2 Q) == r" to
@@ -83,9 +63,12 @@ constexpr uint32_t FLAG_VALID = 1u, FLAG_NEG1 = 2u, FLAG_NEG2 = 4u, FLAG_GLV_OVF
 // batches (hkv_pair_split_kernel, §2c) run the u1 * G sum and the key's
 // square root on their own waves beside the two Q chains and join exactly in
 // the kernel.
-// the small-batch kernel's signature / square-root waves' output for the join (SoA, its own buffer): A = u1 G (24 words), y0 (8), flags
-enum : int { AUX_AX = 0, AUX_Y0 = 24, AUX_FLAGS = 32, AUX_SQ = 33, AUX_WORDS = 34 };  // AUX_SQ: the pair kernel's sqrt wave
-constexpr uint32_t AUXF_AINF = 1u, AUXF_SQ = 2u;
+
+// the lane's flags word (IM_FLAGS)
+constexpr uint32_t FLAG_VALID = 1u;      // the signature and key parse and every check so far passed
+constexpr uint32_t FLAG_NEG1 = 2u;       // the GLV half k1 is negative
+constexpr uint32_t FLAG_NEG2 = 4u;       // the GLV half k2 is negative
+constexpr uint32_t FLAG_GLV_OVF = 8u;    // the GLV split overflowed (unreachable; fails closed)
 constexpr uint32_t FLAG_YODD = 16u;      // the key's y is odd (prefix 03/07, or the 04 key's y)
 constexpr uint32_t FLAG_COMP = 32u;      // compressed key: x^3 + 7 not yet shown to be a square
 constexpr uint32_t FLAG_BINF = 64u;      // B' = u2 * Q' is infinity
@@ -93,17 +76,102 @@ constexpr uint32_t FLAG_DECIDED = 128u;  // the finish kernel decided the verdic
 constexpr uint32_t FLAG_ACCEPT = 256u;   // ... and it is accept
 constexpr uint32_t FLAG_RARE = 512u;     // A or B infinity, or A = +-B: the exact slow path decides
 constexpr uint32_t FLAG_AINF = 1024u;    // A = u1 * G is infinity (u1 = 0)
-enum : int {
-  IM_W = IM_QY,         // 8 limbs, w = x^3 + 7 (normalised)
-  IM_BX = IM_DIG,       // 3 x 8 limbs: B' = (X, Y, Z) Jacobian on E_w (ecmult -> finish)
-  IM_NUM = IM_DIG,      // 3 x 8 limbs: num_r, num_{r+n}, den (finish -> verdict kernel)
-  IM_DEN = IM_DIG + 16,
-  IM_AX = IM_QX,        // rare lanes: A = u1 * G parked over x (8) and K1..U1H (16)
-  IM_AY = IM_K1,
+// the small-batch join's flags word (AUX_FLAGS), and AUX_SQ's value
+constexpr uint32_t AUXF_AINF = 1u, AUXF_SQ = 2u;
+constexpr uint32_t AUXF_STDOK = 4u;  // standard inputs: the script checks passed
+
+// ---------------------------------------------------------------------------
+// The verify intermediates. Every verify launch hands its results to the next
+// through `im` (IM_WORDS word rows per signature); the small-batch kernels
+// also use `aux` (AUX_WORDS). Both are structure-of-arrays: word k of field F
+// of signature i sits at [(F.off + k) * n_pad + i], an index the SoA view of
+// hkv_kernels.hip forms (and the few sites its header comment names). The
+// fields of `im` alias each other by phase: the table names each once, the
+// live sets below it say which hold data at each hand-off, and the
+// static_asserts check that fields live together share no word row at any
+// supported HKV_QW / HKV_GTAB_W (tests/test_im_layout.py compiles them all).
+// ---------------------------------------------------------------------------
+struct Field {
+  int off, len;  // word rows [off, off + len)
 };
-constexpr int IM_RARE_LIST = IM_AY + 16;  // the finish kernel's compacted rare-lane indices
-static_assert(IM_RARE_LIST < IM_R, "A and the rare list fit below r");
-static_assert(IM_DIG + 24 <= IM_GDIG, "B' and num/den fit over the Q digits");
+
+constexpr Field IM_FLAGS = {0, 1};    // FLAG_* of the lane
+constexpr Field IM_QX = {1, 8};       // affine pubkey x (normalised)
+constexpr Field IM_W = {9, 8};        // w = x^3 + 7 (normalised)
+constexpr Field IM_S = {17, 8};       // s after the mode's high-S policy (words 25, 26 unused)
+constexpr Field IM_M = {27, 8};       // m = msg mod n
+constexpr Field IM_R = {35, 8};       // r (< n)
+constexpr Field IM_C = {43, 8};       // batch-inversion prefix product, then s^-1
+constexpr Field IM_DIG = {51, NWIN};  // Q digit word of window w (above), NWIN <= 33
+constexpr Field IM_GDIG = {84, 2 * GWIN};  // G digit words of window j: u1_lo at 2j, u1_hi at 2j + 1
+constexpr int IM_WORDS = IM_GDIG.off + IM_GDIG.len;
+// over the Q digits, once the chains have consumed them
+constexpr Field IM_BX = {IM_DIG.off, 8};         // B' = u2 * Q' = (X, Y, Z), Jacobian on E_w
+constexpr Field IM_BY = {IM_DIG.off + 8, 8};
+constexpr Field IM_BZ = {IM_DIG.off + 16, 8};
+constexpr Field IM_NUM = {IM_DIG.off, 8};        // common lanes: num for the candidate r,
+constexpr Field IM_NUMN = {IM_DIG.off + 8, 8};   //   num for the candidate r + n,
+constexpr Field IM_DEN = {IM_DIG.off + 16, 8};   //   den (y_c = num / den)
+// rare lanes: A = u1 * G parked for hkv_rare_kernel over x, s and m
+constexpr Field IM_AX = {IM_QX.off, 8};
+constexpr Field IM_AY = {IM_S.off, 8};
+constexpr Field IM_AZ = {IM_S.off + 8, 8};
+// one word row indexed by rank, not by lane: entry k is the k-th rare lane's
+// index (the finish kernel compacts them), so it must miss every field any
+// lane still holds. It is word 6 of another lane's m: safe because nothing
+// reads m after hkv_glv_kernel (the lane prologue of standard inputs never
+// stores m), which the live sets from the glv hand-off on state by leaving
+// IM_M out.
+constexpr Field IM_RARE_LIST = {IM_AZ.off + 8, 1};
+
+// aux: the small-batch kernels' signature and square-root waves' output for
+// the in-kernel join
+constexpr Field AUX_AX = {0, 8};
+constexpr Field AUX_AY = {8, 8};
+constexpr Field AUX_AZ = {16, 8};  // A = u1 * G, Jacobian on E
+constexpr Field AUX_Y0 = {24, 8};     // the key's y0 = sqrt(w) of its parity
+constexpr Field AUX_FLAGS = {32, 1};  // AUXF_AINF, AUXF_STDOK
+constexpr Field AUX_SQ = {33, 1};     // AUXF_SQ: w is a square (the sqrt wave's word)
+constexpr int AUX_WORDS = 34;
+
+// What each hand-off carries. A launch may write a field only if no field of
+// the live set it hands on shares its words (and it has read what it needs of
+// the set it was handed).
+constexpr Field LIVE_PROLOGUE_INV[] = {IM_FLAGS, IM_QX, IM_W, IM_R, IM_S, IM_M};
+constexpr Field LIVE_INV_GLV[] = {IM_FLAGS, IM_QX, IM_W, IM_R, IM_S, IM_M, IM_C};
+// from hkv_glv_kernel or the standard-input lane prologue to the table, chain
+// and mid-size kernels (the table build is the last reader of QX; the late
+// standard-input form needs C = s^-1 up to the finish kernel)
+constexpr Field LIVE_GLV_ECMULT[] = {IM_FLAGS, IM_QX, IM_W, IM_R, IM_C, IM_DIG, IM_GDIG};
+constexpr Field LIVE_CHAIN_FINISH[] = {IM_FLAGS, IM_W, IM_R, IM_C, IM_BX, IM_BY, IM_BZ, IM_GDIG};
+// from the finish kernel to hkv_rare_kernel and hkv_yverdict_kernel, per
+// lane one of the two; C is free, and the verdict kernel keeps its prefix
+// products there
+constexpr Field LIVE_FINISH_RARE[] = {IM_FLAGS, IM_W, IM_R, IM_RARE_LIST, IM_AX, IM_AY, IM_AZ, IM_BX, IM_BY, IM_BZ};
+constexpr Field LIVE_FINISH_VERDICT[] = {IM_FLAGS, IM_W, IM_R, IM_RARE_LIST, IM_NUM, IM_NUMN, IM_DEN, IM_C};
+// inside the small-batch kernels and the multisig tail's pair groups
+constexpr Field LIVE_SMALL_IM[] = {IM_FLAGS, IM_R, IM_DIG, IM_GDIG};
+constexpr Field LIVE_SMALL_AUX[] = {AUX_AX, AUX_AY, AUX_AZ, AUX_Y0, AUX_FLAGS, AUX_SQ};
+
+constexpr bool fields_overlap(Field a, Field b) { return a.off < b.off + b.len && b.off < a.off + a.len; }
+// every field inside [0, words) and no two sharing a word row
+template <int N>
+constexpr bool live_set_ok(const Field (&f)[N], int words) {
+  for (int a = 0; a < N; ++a) {
+    if (f[a].off < 0 || f[a].len < 1 || f[a].off + f[a].len > words) return false;
+    for (int b = a + 1; b < N; ++b)
+      if (fields_overlap(f[a], f[b])) return false;
+  }
+  return true;
+}
+static_assert(live_set_ok(LIVE_PROLOGUE_INV, IM_WORDS), "prologue -> inv");
+static_assert(live_set_ok(LIVE_INV_GLV, IM_WORDS), "inv -> glv");
+static_assert(live_set_ok(LIVE_GLV_ECMULT, IM_WORDS), "glv -> table / chain / mid-size");
+static_assert(live_set_ok(LIVE_CHAIN_FINISH, IM_WORDS), "chain -> finish");
+static_assert(live_set_ok(LIVE_FINISH_RARE, IM_WORDS), "finish -> rare");
+static_assert(live_set_ok(LIVE_FINISH_VERDICT, IM_WORDS), "finish -> verdict");
+static_assert(live_set_ok(LIVE_SMALL_IM, IM_WORDS), "small-batch im");
+static_assert(live_set_ok(LIVE_SMALL_AUX, AUX_WORDS), "small-batch aux");
 
 // Fixed-base tables in HBM: multiples j*B for j = 1..2^19, affine, 16 dwords
 // per entry [x(8) | y(8)], table t at entry offset t*2^19: table 2j + h holds
