@@ -35,6 +35,7 @@ module Haskoin.Node.Verify
     verifyRawBatch,
     verifyHashSigBatch,
     verifyStdInputBatch,
+    verifyStdTxBatch,
     txHashBatch,
     BlockCheck (..),
     checkBlocksBatch,
@@ -71,6 +72,7 @@ import Haskoin
     Ctx,
     Hash256,
     Network,
+    OutPoint,
     PubKey,
     ScriptOutput,
     Sig,
@@ -226,6 +228,44 @@ verifyStdInputBatch v net txs ins = withMVar v.lock $ \_ -> do
               c_hkv_verify_std_inputs v.ctx ptxs pjobs (fromIntegral n) forkid bits
                 >>= check "hkv_verify_std_inputs" . fromIntegral
               readBits n bits
+
+-- | Element t equals @verifyStdTx net ctx tx_t prevouts_t@ (haskoin-core
+-- Haskoin.Transaction.Builder): each tx comes with an unordered prevout list
+-- keyed by outpoint, as verifyStdTx takes it. The outpoint match
+-- (matchTemplate: inputs in order, each taking the first entry not yet taken
+-- with its outpoint), verifyStdInput per matched input and the per-tx @all@
+-- run on the GPU; a tx without inputs, with an input that finds no entry, or
+-- that does not parse is False. The network is needed for the fork id, as in
+-- 'verifyStdInputBatch'.
+verifyStdTxBatch :: Verifier -> Network -> [(Tx, [(ScriptOutput, Word64, OutPoint)])] -> IO [Bool]
+verifyStdTxBatch _ _ [] = return []
+verifyStdTxBatch v net xs = withMVar v.lock $ \_ -> do
+  let raws = map (runPutS . serialize . fst) xs
+      offs = scanl (+) 0 (map (fromIntegral . B.length) raws) :: [Word32]
+      entries = concatMap snd xs
+      -- tx t owns entries [poffs !! t, poffs !! (t + 1)), in list order
+      poffs = scanl (+) 0 (map (fromIntegral . length . snd) xs) :: [Word32]
+      scripts = map (\(so, _, _) -> encodeOutputBS so) entries
+      soffs = scanl (+) 0 (map (fromIntegral . B.length) scripts) :: [Word32]
+      srefs = concat [[o, fromIntegral (B.length s)] | (s, o) <- zip scripts soffs] :: [Word32]
+      vals = [val | (_, val, _) <- entries]
+      -- 36 bytes per entry: the hash as it appears in the tx, then the LE32 index
+      ops = B.concat [runPutS (serialize op) | (_, _, op) <- entries]
+      forkid = maybe hkvNoForkId fromIntegral (getSigHashForkId net)
+      n = length xs
+      nw = (n + 31) `div` 32
+  BU.unsafeUseAsCString (B.concat raws) $ \pbytes ->
+    BU.unsafeUseAsCString (B.concat scripts) $ \pscripts ->
+      BU.unsafeUseAsCString ops $ \pops ->
+        withArray offs $ \poffsets ->
+          withArray poffs $ \pprev ->
+            withArray srefs $ \psrefs ->
+              withArray vals $ \pvals ->
+                with (HkvTxs (castPtr pbytes) poffsets (fromIntegral n) (castPtr pscripts) (last soffs)) $ \ptxs ->
+                  allocaArray nw $ \bits -> do
+                    c_hkv_verify_std_txs v.ctx ptxs pprev (castPtr pops) psrefs pvals forkid bits
+                      >>= check "hkv_verify_std_txs" . fromIntegral
+                    readBits n bits
 
 -- | The serialised txs of a batch as an @hkv_txs@ without a script pool:
 -- each tx's @runPutS . serialize@ back to back, offsets as prefix sums.

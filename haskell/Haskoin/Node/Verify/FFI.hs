@@ -23,6 +23,7 @@ module Haskoin.Node.Verify.FFI
     c_hkv_batch_capacity,
     c_hkv_verify,
     c_hkv_verify_std_inputs,
+    c_hkv_verify_std_txs,
     c_hkv_verify_std_inputs_device_status,
     c_hkv_device_fault,
     c_hkv_device_healthy,
@@ -173,6 +174,14 @@ foreign import ccall safe "hkv_verify"
 
 foreign import ccall safe "hkv_verify_std_inputs"
   c_hkv_verify_std_inputs :: Ptr HkvCtx -> Ptr HkvTxs -> Ptr InputJob -> CSize -> Int32 -> Ptr Word32 -> IO CInt
+
+-- Batch verifyStdTx: txs, then the prevout lists as four plain arrays —
+-- prev_offsets (n_tx + 1 entry indices, one list per tx), prev_outpoints (36
+-- wire bytes per entry), prev_scripts ((offset, length) into the script pool
+-- per entry), prev_values — the fork id, and ceil(n_tx/32) words of tx verdicts.
+foreign import ccall safe "hkv_verify_std_txs"
+  c_hkv_verify_std_txs ::
+    Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word32 -> Ptr Word8 -> Ptr Word32 -> Ptr Word64 -> Int32 -> Ptr Word32 -> IO CInt
 
 -- The asynchronous block path: everything is enqueued on the caller's HIP
 -- stream (the last argument); d_status gets HKV_STATUS_* bits ORed in on it.

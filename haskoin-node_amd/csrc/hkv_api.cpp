@@ -131,6 +131,11 @@ struct DevCtx {
   // header batch, the merkle / block batch
   DevBuf<uint8_t> stage_tx_bytes, stage_scripts, stage_jobs, stage_out, stage_headers, stage_blocks;
   DevBuf<uint32_t> stage_tx_off;
+  // the host form of batch verifyStdTx (hkv_verify_std_txs): the staged prevout
+  // arrays, the input prefix sums, the jobs built on device, the tx verdict words
+  DevBuf<uint8_t> stage_prev;
+  DevBuf<uint32_t> std_first, host_tx_bits;
+  DevBuf<hkv_input_job> std_jobs;
   // multisig inputs (hkv_sighash.hip section 4, hkv_kernels.hip 2e): desc
   // words, offsets, candidate and key-check verdict words, the candidate then
   // the key records; the host form's verdict words
@@ -696,7 +701,7 @@ class Call {
 
 extern "C" {
 
-uint32_t hkv_version(void) { return (1u << 16) | 1u; }
+uint32_t hkv_version(void) { return (1u << 16) | 2u; }
 
 const char* hkv_strerror(int err) {
   switch (err) {
@@ -1459,5 +1464,152 @@ int hkv_check_blocks(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* block_off
   return c.done();
 }
 
-}  // extern "C"
+// ---- batch verifyStdTx -------------------------------------------------------
 
+// the device arrays of a batch's prevout lists (include/hkv.h)
+static bool prevouts_ok(const uint32_t* off, const uint8_t* outpoints, const uint32_t* scripts,
+                        const uint64_t* values) {
+  return off && outpoints && scripts && values && aligned(off, 4) && aligned(scripts, 4) && aligned(values, 8);
+}
+
+int hkv_std_tx_jobs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                           const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                           const uint64_t* d_prev_values, size_t n_inputs, uint32_t* d_input_first,
+                           hkv_input_job* d_jobs, uint32_t* d_status, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
+  if (!prevouts_ok(d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values) || !d_input_first ||
+      !d_status || (n_inputs && !d_jobs) || !aligned(d_input_first, 4) || !aligned(d_status, 4) ||
+      !aligned(d_jobs, 8) || !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  HKV_TRY(hkv::launch_stdtx_counts(d_txs->bytes, d_txs->offsets, d_txs->n_tx, (uint32_t)n_inputs, d_input_first,
+                                   d_status, c.st),
+          "input count launch");
+  HKV_TRY(hkv::launch_stdtx_jobs(d_txs->bytes, d_txs->offsets, d_txs->n_tx, d_input_first,
+                                 hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values},
+                                 (uint32_t)n_inputs, d_jobs, c.st),
+          "job builder launch");
+  return HKV_OK;
+}
+
+int hkv_tx_verdicts_device(hkv_ctx* ctx, int dev, const uint32_t* d_input_first, size_t n_tx,
+                           const uint32_t* d_input_bits, uint32_t* d_tx_bits, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || n_tx >= 0xFFFFFF00ull) return HKV_E_ARG;
+  if (n_tx == 0) return HKV_OK;
+  if (!d_input_first || !d_input_bits || !d_tx_bits || !aligned(d_input_first, 4) || !aligned(d_input_bits, 4) ||
+      !aligned(d_tx_bits, 4))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  HKV_TRY(hkv::launch_tx_verdicts(d_input_first, (uint32_t)n_tx, d_input_bits, nullptr, d_tx_bits, c.st),
+          "tx verdict launch");
+  return HKV_OK;
+}
+
+// the three stages of batch verifyStdTx on c's stream (the caller holds the
+// Tx lock and has acquired the scratch with status as the call's status word)
+static int enqueue_verify_std_txs(Call& c, const hkv_txs* dt, const hkv::StdPrevouts& p, int32_t forkid,
+                                  size_t n_inputs, uint32_t* first, hkv_input_job* jobs, void* recs,
+                                  uint32_t* input_bits, uint32_t* tx_bits, uint32_t* status, bool counted) {
+  if (!counted)
+    HKV_TRY(hkv::launch_stdtx_counts(dt->bytes, dt->offsets, dt->n_tx, (uint32_t)n_inputs, first, status, c.st),
+            "input count launch");
+  HKV_TRY(hkv::launch_stdtx_jobs(dt->bytes, dt->offsets, dt->n_tx, first, p, (uint32_t)n_inputs, jobs, c.st),
+          "job builder launch");
+  if (n_inputs) HKV_RC(enqueue_verify_std_inputs(c.d, dt, jobs, n_inputs, forkid, recs, input_bits, c.st));
+  HKV_TRY(hkv::launch_tx_verdicts(first, dt->n_tx, input_bits, status, tx_bits, c.st), "tx verdict launch");
+  return HKV_OK;
+}
+
+int hkv_verify_std_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                              const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                              const uint64_t* d_prev_values, int32_t forkid, size_t n_inputs,
+                              uint32_t* d_input_first, hkv_input_job* d_jobs, void* d_records,
+                              uint32_t* d_input_bits, uint32_t* d_tx_bits, uint32_t* d_status, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
+  if (d_txs->n_tx == 0) return HKV_OK;
+  if (!prevouts_ok(d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values) || !d_input_first ||
+      !d_tx_bits || !d_status || (n_inputs && (!d_jobs || !d_records || !d_input_bits)) ||
+      !aligned(d_input_first, 4) || !aligned(d_status, 4) || !aligned(d_jobs, 8) || !aligned(d_input_bits, 4) ||
+      !aligned(d_tx_bits, 4) || !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::Tx);
+  int rc = c.acquire(d_status);
+  if (!rc)
+    rc = enqueue_verify_std_txs(c, d_txs, hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values},
+                                forkid, n_inputs, d_input_first, d_jobs, d_records, d_input_bits, d_tx_bits, d_status,
+                                false);
+  return c.done(rc);
+}
+
+int hkv_verify_std_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                       const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                       int32_t forkid, uint32_t* tx_verdict_bits) {
+  if (!ctx || ctx->devs.empty() || !txs_ok(txs)) return HKV_E_ARG;
+  const size_t n_tx = txs->n_tx;
+  if (n_tx == 0) return HKV_OK;
+  if (!prev_offsets || !tx_verdict_bits || !tx_offsets_sorted(txs)) return HKV_E_ARG;
+  for (size_t t = 0; t < n_tx; ++t)
+    if (prev_offsets[t + 1] < prev_offsets[t]) return HKV_E_ARG;
+  const size_t e0 = prev_offsets[0], n_ent = prev_offsets[n_tx] - e0;
+  if (n_ent && (!prev_outpoints || !prev_scripts || !prev_values)) return HKV_E_ARG;
+  Call c(ctx, 0, Lock::Tx);
+  DevCtx& d = c.d;
+  hkv_txs dt;
+  void* unused = nullptr;
+  uint32_t* status = reinterpret_cast<uint32_t*>(d.ms_bar + MS_HOST_STATUS);
+  // one staging buffer: values | entry offsets | script references | outpoints.
+  // Only the entries the offsets name are staged, so the staged offsets are
+  // rebased by the first one on the host.
+  hkv::Layout l;
+  const size_t o_val = l.add(n_ent * 8, 8), o_off = l.add((n_tx + 1) * 4, 4), o_scr = l.add(n_ent * 8, 4),
+               o_op = l.add(n_ent * 36, 4);
+  std::vector<uint32_t> rebased(n_tx + 1);
+  for (size_t t = 0; t <= n_tx; ++t) rebased[t] = (uint32_t)(prev_offsets[t] - e0);
+  HKV_RC(c.acquire(status));
+  HKV_RC(stage_txs(d, txs, nullptr, 0, &dt, &unused));
+  HKV_RC(d.stage_prev.reserve(l.total, "hipMalloc(prevouts)"));
+  HKV_RC(d.std_first.reserve(n_tx + 1, "hipMalloc(input offsets)"));
+  HKV_RC(d.host_tx_bits.reserve((n_tx + 63) / 64 * 2, "hipMalloc(tx verdict words)"));
+  uint8_t* b = d.stage_prev;
+  const hkv::StdPrevouts p{reinterpret_cast<const uint32_t*>(b + o_off), b + o_op,
+                           reinterpret_cast<const uint32_t*>(b + o_scr),
+                           reinterpret_cast<const uint64_t*>(b + o_val)};
+  HKV_TRY(hipMemcpyAsync(b + o_off, rebased.data(), (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D prevout offsets");
+  if (n_ent) {
+    HKV_TRY(hipMemcpyAsync(b + o_op, prev_outpoints + e0 * 36, n_ent * 36, hipMemcpyHostToDevice, c.st),
+            "H2D prevout outpoints");
+    HKV_TRY(hipMemcpyAsync(b + o_scr, prev_scripts + e0 * 2, n_ent * 8, hipMemcpyHostToDevice, c.st),
+            "H2D prevout scripts");
+    HKV_TRY(hipMemcpyAsync(b + o_val, prev_values + e0, n_ent * 8, hipMemcpyHostToDevice, c.st), "H2D prevout values");
+  }
+  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
+  // the input total sizes the scratch: counted on the device, read back once
+  // (the count's own status bit is dropped: the total is not known before it)
+  uint32_t total = 0;
+  HKV_TRY(hkv::launch_stdtx_counts(dt.bytes, dt.offsets, dt.n_tx, 0, d.std_first, status, c.st), "input count launch");
+  HKV_TRY(hipMemcpyAsync(&total, d.std_first + n_tx, sizeof(total), hipMemcpyDeviceToHost, c.st), "D2H input total");
+  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
+  HKV_TRY(hipStreamSynchronize(c.st), "input count sync");
+  const size_t n = total;
+  if (n > HKV_MAX_STD_INPUTS) return c.done(HKV_E_ARG);
+  HKV_RC(d.std_jobs.reserve(n, "hipMalloc(jobs)"));
+  HKV_RC(d.recs.reserve(n * hkv::REC_SIZE, "hipMalloc(records)"));
+  HKV_RC(d.host_std_bits.reserve((n + 63) / 64 * 2, "hipMalloc(verdict words)"));
+  HKV_RC(enqueue_verify_std_txs(c, &dt, p, forkid, n, d.std_first, d.std_jobs, d.recs, d.host_std_bits,
+                                d.host_tx_bits, status, true));
+  // (the tx words come in pairs per 64 txs; the caller gets ceil(n_tx/32))
+  HKV_TRY(hipMemcpyAsync(tx_verdict_bits, d.host_tx_bits, (n_tx + 31) / 32 * 4, hipMemcpyDeviceToHost, c.st),
+          "D2H tx bits");
+  uint32_t fault = 0;
+  HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
+  HKV_TRY(hipStreamSynchronize(c.st), "std txs sync");
+  if (fault & HKV_STATUS_TAIL_FAULT) {
+    g_last_hip = "multisig tail: work-queue wait timed out";
+    return c.done(HKV_E_INTERNAL);
+  }
+  return c.done();
+}
+
+}  // extern "C"

@@ -205,6 +205,28 @@ hipError_t launch_tx_hashes_only(const uint8_t* txs, const uint32_t* tx_off, uin
                                  uint32_t* txt, hipStream_t st);
 // multisig inputs: the scan (hkv_sighash.hip section 4; the tail in hkv_kernels.hip)
 hipError_t launch_ms_scan(const StdOps& o, uint32_t n, const MsScan& ms, hipStream_t st);
+// hkv_stdtx.hip: batch verifyStdTx around the standard-input verify.
+// Tx t's prevout list is entries [offsets[t], offsets[t+1]): entry e has the
+// outpoint outpoints[36e, 36e + 36), the script scripts[2e] (offset into the
+// batch's script pool), scripts[2e + 1] (length) and the amount values[e].
+struct StdPrevouts {
+  const uint32_t* offsets;
+  const uint8_t* outpoints;
+  const uint32_t* scripts;
+  const uint64_t* values;
+};
+// input_first[0, n_tx]: the exclusive prefix sums of the txs' input counts (0
+// for a tx that does not parse), the total last; a total other than n_inputs
+// ORs HKV_STATUS_INPUT_COUNT into status. Two launches.
+hipError_t launch_stdtx_counts(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, uint32_t n_inputs,
+                               uint32_t* input_first, uint32_t* status, hipStream_t st);
+// one job per input in tx-major order from the matched prevouts; exactly n_inputs jobs are written
+hipError_t launch_stdtx_jobs(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, const uint32_t* input_first,
+                             const StdPrevouts& p, uint32_t n_inputs, hkv_input_job* jobs, hipStream_t st);
+// tx bit t = all of input_bits[input_first[t], input_first[t+1]) and the range is not empty; ceil(n_tx/64)*2
+// words. status (or null): every bit is 0 once it holds HKV_STATUS_INPUT_COUNT
+hipError_t launch_tx_verdicts(const uint32_t* input_first, uint32_t n_tx, const uint32_t* input_bits,
+                              const uint32_t* status, uint32_t* tx_bits, hipStream_t st);
 // hkv_headers.hip
 hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_limit, const uint8_t* prev0,
                           uint8_t* hashes, uint8_t* status, hipStream_t st);

@@ -13,6 +13,8 @@ from .headers import check_headers, check_headers_device
 from .merkle import merkle_roots, merkle_roots_device
 from .blocks import check_blocks, check_blocks_device, split_block, tx_ids, tx_ids_device
 from .sighash import TxBatch, tx_sig_hash_batch, verify_std_inputs
+from .stdtx import (pack_prevouts, std_tx_jobs_device, tx_verdicts_device, verify_std_txs, verify_std_txs_detail,
+                    verify_std_txs_device)
 from .verify import (Verifier, VerifierConfig, verify_hash_sig_batch,
                      verify_raw_batch)
 from .actor import VerifyActor, VerifyActorConfig
@@ -25,5 +27,7 @@ __all__ = [
     "verify_std_inputs", "check_headers", "check_headers_device",
     "merkle_roots", "merkle_roots_device", "VerifyActor", "VerifyActorConfig",
     "tx_ids", "tx_ids_device", "split_block", "check_blocks", "check_blocks_device",
+    "verify_std_txs", "verify_std_txs_detail", "verify_std_txs_device", "std_tx_jobs_device", "tx_verdicts_device",
+    "pack_prevouts",
     "HKV_TXID_OK", "HKV_TXID_BAD_TX", "HKV_BLK_MERKLE_OK", "HKV_BLK_MUTATED", "HKV_BLK_BAD_TX", "HKV_BLK_EMPTY",
 ]

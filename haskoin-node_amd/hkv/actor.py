@@ -14,6 +14,11 @@ a mailbox drained by one loop.
   makes ONE call for the whole batch (tx k of the batch is tx index k of the
   call). A message that does not fit (a block, or a tx past the bound) is held
   over and handled next, so the mailbox order is kept.
+* **Whole txs.** ``verify_std_tx`` posts a tx with an outpoint-keyed prevout
+  list (haskoin-core ``verifyStdTx``): the outpoint match, the inputs'
+  verdicts and the tx verdict come from one ``verify_std_txs_detail`` call, so
+  the caller numbers no inputs. It is its own call, in mailbox order; a failed
+  call is re-submitted like any other, but there is no CPU fallback for it.
 * **Errors.** A failed call (``HkvError``: HKV_E_INTERNAL when the call's
   multisig tail gave up, a device error) is re-submitted to the GPU up to
   ``retries`` times, then handed to ``fallback`` — in the Haskell actor,
@@ -35,6 +40,7 @@ from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 from .lib import HkvError
 from .sighash import verify_std_inputs
+from .stdtx import verify_std_txs_detail
 
 # Outcomes published per message (VerifyEvent in the Haskell module).
 
@@ -79,6 +85,13 @@ class _Block:
     key: Any
     txs: Sequence[bytes]
     inputs: Sequence[Tuple[int, int, bytes, int]]  # (tx index, input index, prevout scriptPubKey, value)
+
+
+@dataclass
+class _StdTx:
+    key: Any
+    tx: bytes
+    prevouts: Sequence[Tuple[bytes, bytes, int]]  # (36-byte wire outpoint, prevout scriptPubKey, value), any order
 
 
 _STOP = object()
@@ -129,6 +142,13 @@ class VerifyActor:
     def verify_block(self, key, txs: Sequence[bytes], inputs: Sequence[Tuple[int, int, bytes, int]]) -> None:
         self._post(_Block(key, list(txs), list(inputs)))
 
+    def verify_std_tx(self, key, tx: bytes, prevouts: Sequence[Tuple[bytes, bytes, int]]) -> None:
+        """verifyStdTx: the prevouts are matched to the tx's inputs by
+        outpoint on the device; publishes TxVerified, or TxRejected with the
+        inputs that fail or found no prevout (none for a tx without inputs
+        or one that does not parse)."""
+        self._post(_StdTx(key, tx, list(prevouts)))
+
     def _post(self, msg) -> None:
         if self._crash is not None:
             raise RuntimeError("verify actor stopped on an error") from self._crash
@@ -166,6 +186,9 @@ class VerifyActor:
                     return
                 if isinstance(msg, _Block):
                     self._handle_block(msg)
+                    continue
+                if isinstance(msg, _StdTx):
+                    self._handle_std_tx(msg)
                     continue
                 batch, n = [msg], len(msg.inputs)
                 deadline = time.monotonic() + self.cfg.max_wait_s
@@ -209,6 +232,23 @@ class VerifyActor:
                 return None, err
             return ok, None
         return None, err
+
+    def _handle_std_tx(self, m: _StdTx) -> None:
+        err = None
+        for _ in range(1 + self.cfg.retries):
+            self.stats.gpu_calls += 1
+            try:
+                ok, per_input = verify_std_txs_detail(self.v, [m.tx], [m.prevouts], self.cfg.forkid)
+            except HkvError as e:
+                self.stats.gpu_failures += 1
+                err = str(e)
+                self.stats.errors.append(err)
+                continue
+            self.stats.batch_inputs.append(len(per_input[0]))
+            bad = tuple(i for i, v in enumerate(per_input[0]) if not v)
+            self.publish(TxVerified(m.key) if ok[0] else TxRejected(m.key, bad))
+            return
+        self.publish(VerifyFailed(m.key, err))
 
     def _handle_block(self, m: _Block) -> None:
         ok, err = self._verify(m.txs, m.inputs) if m.inputs else ([], None)

@@ -25,6 +25,7 @@ HKV_BLK_MERKLE_OK, HKV_BLK_MUTATED, HKV_BLK_BAD_TX, HKV_BLK_EMPTY = 0x01, 0x02, 
 HKV_OK = 0
 HKV_FAIL_NONE, HKV_FAIL_ENQUEUE, HKV_FAIL_JOIN, HKV_FAIL_ALLOC, HKV_FAIL_TAIL = 0, 1, 2, 3, 4
 HKV_STATUS_TAIL_FAULT = 1
+HKV_STATUS_INPUT_COUNT = 2
 _ERRS = {-1: "HKV_E_ARG", -2: "HKV_E_NODEV", -3: "HKV_E_OOM", -4: "HKV_E_HIP", -5: "HKV_E_INTERNAL"}
 
 _PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,6 +103,14 @@ EXPORTS = {
     "hkv_device_fault": (c_int, [c_void_p, c_int, POINTER(c_uint32)]),
     "hkv_verify_std_inputs": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_size_t, ctypes.c_int32,
                                       POINTER(c_uint32)]),
+    "hkv_std_tx_jobs_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hkv_tx_verdicts_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "hkv_verify_std_txs_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
+                                          ctypes.c_int32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    "hkv_verify_std_txs": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int32,
+                                   POINTER(c_uint32)]),
     "hkv_merkle_roots": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "hkv_merkle_roots_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),

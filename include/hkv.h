@@ -33,6 +33,14 @@
  *       (strict DER, low S, hashtype), the HASH160 / SHA-256 script checks,
  *       legacy or BIP143 sighash, verifyHashSig and the countMulSig walk,
  *       all on device.
+ *   hkv_verify_std_txs / hkv_verify_std_txs_device
+ *       replaces N calls of haskoin-core
+ *       `verifyStdTx :: Network -> Ctx -> Tx -> [(ScriptOutput, Word64, OutPoint)] -> Bool`
+ *       (Haskoin.Transaction.Builder): matchTemplate of each tx's unordered
+ *       prevout list against its inputs by outpoint, verifyStdInput per
+ *       matched input, one verdict per tx. hkv_std_tx_jobs_device is the
+ *       matching alone (the prevout provider), hkv_tx_verdicts_device the
+ *       per-tx `all`.
  *   hkv_check_headers / hkv_check_headers_device
  *       replaces the per-header part of haskoin-core `connectBlocks` reached
  *       from importHeaders (/root/reference/src/Haskoin/Node/Chain.hs:500-520):
@@ -330,6 +338,81 @@ int hkv_device_fault(hkv_ctx* ctx, int dev, uint32_t* fault);
  * HKV_STATUS_TAIL_FAULT (some multisig verdicts stayed 0). */
 int hkv_verify_std_inputs(hkv_ctx* ctx, const hkv_txs* txs, const hkv_input_job* jobs, size_t n, int32_t forkid,
                           uint32_t* verdict_bits);
+
+/* ---------------------------------------------------------------------------
+ * Batch verifyStdTx: whole transactions against outpoint-keyed prevout lists.
+ *
+ *   verifyStdTx net ctx tx xs =
+ *       not (null tx.inputs) && all go (zip (matchTemplate xs tx.inputs f) [0..])
+ *     where f (_,_,o) txin = o == txin.outpoint
+ *           go (Just (so,val,_), i) = verifyStdInput net ctx tx i so val
+ *           go _                    = False
+ *
+ * The prevouts of a batch are four plain arrays. Tx t owns the entries
+ * [prev_offsets[t], prev_offsets[t+1]) (n_tx + 1 non-decreasing entry
+ * indices: one list per tx, as verifyStdTx takes it), in list order. Entry e:
+ *   outpoint      prev_outpoints[36e, 36e + 36), wire form: the 32 hash bytes
+ *                 as they appear in the tx, then the LE32 index;
+ *   scriptPubKey  scripts[prev_scripts[2e], + prev_scripts[2e + 1]) of the
+ *                 batch's script pool (hkv_txs);
+ *   amount        prev_values[e].
+ * matchTemplate: inputs are served in input order and input i takes the first
+ * entry in list order, not yet taken, whose outpoint equals its own. So when d
+ * earlier inputs of the tx carry the same outpoint, input i gets the (d+1)-th
+ * entry with that outpoint, or none. A tx is false when an input finds no
+ * entry, when it has no inputs, and when it does not parse (it then counts as
+ * having no inputs); entries no input takes are ignored.
+ * ------------------------------------------------------------------------ */
+/* HKV_STATUS_INPUT_COUNT: the batch's txs hold another number of inputs than
+ * the caller's n_inputs (hkv_std_tx_jobs_device, hkv_verify_std_txs_device). */
+#define HKV_STATUS_INPUT_COUNT 2u
+/* The prevout provider alone. Every pointer in HBM of device `dev`
+ * (d_prev_offsets, d_prev_scripts, d_input_first, d_status 4-byte aligned;
+ * d_prev_values, d_jobs 8-byte aligned); the caller vouches for
+ * d_prev_offsets as for the tx offsets. Writes d_input_first[n_tx + 1], the
+ * exclusive prefix sums of the txs' input counts (0 for a tx that does not
+ * parse; the last entry is the batch's total), and exactly n_inputs jobs into
+ * d_jobs, input i of tx t at d_input_first[t] + i: (t, i, the matched entry's
+ * script and amount), for an input without an entry (t, i, script_len 0),
+ * which no template matches. n_inputs is the caller's total and d_jobs's
+ * capacity: when the txs hold another number of inputs HKV_STATUS_INPUT_COUNT
+ * is ORed into d_status (the caller zeroes it), the jobs that fit are written
+ * and slots past the device's total get jobs that never verify
+ * (tx = 0xFFFFFFFF). Enqueued on hip_stream, not synchronised; stateless as
+ * hkv_tx_ids_device. n_inputs <= 0xFFFFFF00. */
+int hkv_std_tx_jobs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                           const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                           const uint64_t* d_prev_values, size_t n_inputs, uint32_t* d_input_first,
+                           hkv_input_job* d_jobs, uint32_t* d_status, void* hip_stream);
+/* The per-tx reduction alone: tx bit t = 1 iff [d_input_first[t],
+ * d_input_first[t+1]) is not empty and every bit of d_input_bits in it is 1.
+ * Writes ceil(n_tx/64)*2 words to d_tx_bits. The caller vouches that
+ * d_input_bits holds d_input_first[n_tx] bits. Enqueued, stateless. */
+int hkv_tx_verdicts_device(hkv_ctx* ctx, int dev, const uint32_t* d_input_first, size_t n_tx,
+                           const uint32_t* d_input_bits, uint32_t* d_tx_bits, void* hip_stream);
+/* Batch verifyStdTx on device: hkv_std_tx_jobs_device, then
+ * hkv_verify_std_inputs_device_status on the jobs it built, then
+ * hkv_tx_verdicts_device, all enqueued on hip_stream with no host wait
+ * (ASYNCHRONOUS as hkv_verify_std_inputs_device). The caller supplies its
+ * input total n_inputs and the scratch: d_input_first (n_tx + 1 words), d_jobs
+ * (n_inputs jobs), d_records (n_inputs * 168 bytes), d_input_bits
+ * (ceil(n_inputs/64)*2 words). Out: d_tx_bits (ceil(n_tx/64)*2 words) and
+ * d_status (zeroed by the caller; HKV_STATUS_* ORed in). d_input_first and
+ * d_input_bits stay readable: input i of tx t is bit d_input_first[t] + i.
+ * With HKV_STATUS_INPUT_COUNT set every tx bit is 0. */
+int hkv_verify_std_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                              const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                              const uint64_t* d_prev_values, int32_t forkid, size_t n_inputs,
+                              uint32_t* d_input_first, hkv_input_job* d_jobs, void* d_records,
+                              uint32_t* d_input_bits, uint32_t* d_tx_bits, uint32_t* d_status, void* hip_stream);
+/* Host-memory form; writes ceil(n_tx/32) words of tx verdicts. First device,
+ * blocking. The inputs are counted on the device and the 4-byte total is read
+ * back (the one synchronisation this form adds) to size the scratch of the
+ * composed call. HKV_E_ARG for decreasing prev_offsets or tx offsets;
+ * HKV_E_INTERNAL as hkv_verify_std_inputs on a multisig tail fault. */
+int hkv_verify_std_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                       const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                       int32_t forkid, uint32_t* tx_verdict_bits);
 
 /* ---------------------------------------------------------------------------
  * Header batches: the data-parallel part of
