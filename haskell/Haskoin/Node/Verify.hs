@@ -36,6 +36,7 @@ module Haskoin.Node.Verify
     verifyHashSigBatch,
     verifyStdInputBatch,
     verifyStdTxBatch,
+    verifyBlockTxBatch,
     txHashBatch,
     BlockCheck (..),
     checkBlocksBatch,
@@ -266,6 +267,52 @@ verifyStdTxBatch v net xs = withMVar v.lock $ \_ -> do
                     c_hkv_verify_std_txs v.ctx ptxs pprev (castPtr pops) psrefs pvals forkid bits
                       >>= check "hkv_verify_std_txs" . fromIntegral
                     readBits n bits
+
+-- | 'verifyStdTxBatch' for the txs of whole blocks, in block order: each tx
+-- comes with the prevouts the caller's UTXO set has, and an input whose
+-- prevout is not among them is looked up among the EARLIER txs of the batch by
+-- the txHash the GPU computes (the smallest index wins; a tx spends neither a
+-- later tx nor itself). Element t equals @verifyStdTx net ctx tx_t@ on its
+-- list extended by those outputs, so the caller parses, hashes and copies
+-- nothing for in-block spends. A coinbase finds nothing and is False, as under
+-- verifyStdTx: the caller skips element 0 of a block. The second component is
+-- per tx and input the source of its prevout: 'hkvSrcList', 'hkvSrcNone' or
+-- the parent's index in the batch, from which the caller does its double-spend
+-- and UTXO accounting.
+verifyBlockTxBatch :: Verifier -> Network -> [(Tx, [(ScriptOutput, Word64, OutPoint)])] -> IO ([Bool], [[Word32]])
+verifyBlockTxBatch _ _ [] = return ([], [])
+verifyBlockTxBatch v net xs = withMVar v.lock $ \_ -> do
+  let raws = map (runPutS . serialize . fst) xs
+      offs = scanl (+) 0 (map (fromIntegral . B.length) raws) :: [Word32]
+      entries = concatMap snd xs
+      poffs = scanl (+) 0 (map (fromIntegral . length . snd) xs) :: [Word32]
+      scripts = map (\(so, _, _) -> encodeOutputBS so) entries
+      soffs = scanl (+) 0 (map (fromIntegral . B.length) scripts) :: [Word32]
+      srefs = concat [[o, fromIntegral (B.length s)] | (s, o) <- zip scripts soffs] :: [Word32]
+      vals = [val | (_, val, _) <- entries]
+      ops = B.concat [runPutS (serialize op) | (_, _, op) <- entries]
+      forkid = maybe hkvNoForkId fromIntegral (getSigHashForkId net)
+      n = length xs
+      nw = (n + 31) `div` 32
+      nin = sum (map (length . (.inputs) . fst) xs)
+  BU.unsafeUseAsCString (B.concat raws) $ \pbytes ->
+    BU.unsafeUseAsCString (B.concat scripts) $ \pscripts ->
+      BU.unsafeUseAsCString ops $ \pops ->
+        withArray offs $ \poffsets ->
+          withArray poffs $ \pprev ->
+            withArray srefs $ \psrefs ->
+              withArray vals $ \pvals ->
+                with (HkvTxs (castPtr pbytes) poffsets (fromIntegral n) (castPtr pscripts) (last soffs)) $ \ptxs ->
+                  allocaArray nw $ \bits ->
+                    allocaArray (n + 1) $ \pfirst ->
+                      allocaArray (max 1 nin) $ \psrc -> do
+                        c_hkv_verify_block_txs v.ctx ptxs pprev (castPtr pops) psrefs pvals forkid bits pfirst psrc
+                          (fromIntegral nin)
+                          >>= check "hkv_verify_block_txs" . fromIntegral
+                        oks <- readBits n bits
+                        first <- map fromIntegral <$> peekArray (n + 1) pfirst :: IO [Int]
+                        srcs <- peekArray (last first) psrc
+                        return (oks, [take (e - b) (drop b srcs) | (b, e) <- zip first (tail first)])
 
 -- | The serialised txs of a batch as an @hkv_txs@ without a script pool:
 -- each tx's @runPutS . serialize@ back to back, offsets as prefix sums.

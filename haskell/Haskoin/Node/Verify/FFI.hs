@@ -24,6 +24,9 @@ module Haskoin.Node.Verify.FFI
     c_hkv_verify,
     c_hkv_verify_std_inputs,
     c_hkv_verify_std_txs,
+    c_hkv_verify_block_txs,
+    hkvSrcNone,
+    hkvSrcList,
     c_hkv_verify_std_inputs_device_status,
     c_hkv_device_fault,
     c_hkv_device_healthy,
@@ -133,6 +136,13 @@ hkvEInternal = -5
 hkvStatusTailFault :: Word32
 hkvStatusTailFault = 1
 
+-- | HKV_SRC_NONE / HKV_SRC_LIST: an input_src word of hkv_verify_block_txs
+-- that is no parent index — the input found no prevout, or took it from its
+-- tx's own list.
+hkvSrcNone, hkvSrcList :: Word32
+hkvSrcNone = 0xFFFFFFFF
+hkvSrcList = 0xFFFFFFFE
+
 -- | HKV_TXID_BAD_TX: the per-tx status of a tx that does not parse (its txid
 -- is 32 zero bytes).
 hkvTxidBadTx :: Word8
@@ -182,6 +192,16 @@ foreign import ccall safe "hkv_verify_std_inputs"
 foreign import ccall safe "hkv_verify_std_txs"
   c_hkv_verify_std_txs ::
     Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word32 -> Ptr Word8 -> Ptr Word32 -> Ptr Word64 -> Int32 -> Ptr Word32 -> IO CInt
+
+-- Batch verifyStdTx for whole blocks: as hkv_verify_std_txs, but an input its
+-- tx's list has no entry for is looked up among the earlier txs of the batch
+-- by the device-computed txHash. Then input_first (n_tx + 1 words or nullPtr),
+-- input_src (per input: hkvSrcList, hkvSrcNone or the parent's tx index; or
+-- nullPtr) and the room input_src has, in words.
+foreign import ccall safe "hkv_verify_block_txs"
+  c_hkv_verify_block_txs ::
+    Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word32 -> Ptr Word8 -> Ptr Word32 -> Ptr Word64 -> Int32 -> Ptr Word32 ->
+    Ptr Word32 -> Ptr Word32 -> CSize -> IO CInt
 
 -- The asynchronous block path: everything is enqueued on the caller's HIP
 -- stream (the last argument); d_status gets HKV_STATUS_* bits ORed in on it.

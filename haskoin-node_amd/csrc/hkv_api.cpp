@@ -9,16 +9,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
+#include <random>
 #include <string>
 #include <vector>
 
 #include "../../include/hkv.h"
+#include "hkv_blocktx.h"
 #include "hkv_internal.h"
 #include "hkv_launch_plan.h"
 #include "hkv_layout.h"
@@ -136,6 +139,10 @@ struct DevCtx {
   DevBuf<uint8_t> stage_prev;
   DevBuf<uint32_t> std_first, host_tx_bits;
   DevBuf<hkv_input_job> std_jobs;
+  // the host form of hkv_verify_block_txs: the txids, their table, the src words
+  DevBuf<uint8_t> blk_txids;
+  DevBuf<uint32_t> blk_table, blk_src;
+  uint32_t txid_mask = 0xFFFFFFFFu;  // hkv_debug_txid_hash_mask: ANDed into the slot hash of later calls
   // multisig inputs (hkv_sighash.hip section 4, hkv_kernels.hip 2e): desc
   // words, offsets, candidate and key-check verdict words, the candidate then
   // the key records; the host form's verdict words
@@ -184,6 +191,9 @@ struct hkv_ctx {
   // many shards each has failed
   std::vector<bool> healthy;
   std::vector<uint32_t> failures;
+  // the salt of the txid table's slot hash (hkv_blocktx.h), drawn at open and
+  // never changed: which txids share a probe chain is not known outside the process
+  uint64_t txid_salt = 0;
 };
 struct hkv_batch {
   hkv_ctx* ctx = nullptr;
@@ -701,7 +711,7 @@ class Call {
 
 extern "C" {
 
-uint32_t hkv_version(void) { return (1u << 16) | 2u; }
+uint32_t hkv_version(void) { return (1u << 16) | 3u; }
 
 const char* hkv_strerror(int err) {
   switch (err) {
@@ -730,6 +740,15 @@ int hkv_open_devices(const int* device_ids, int n_ids, uint32_t flags, hkv_ctx**
   ctx->devs.resize(n_ids);
   ctx->healthy.assign(n_ids, true);
   ctx->failures.assign(n_ids, 0);
+  // (no exception crosses the ABI: without an entropy source the salt is a
+  // mix of the clock and the context's address, unknown to a peer all the same)
+  try {
+    std::random_device rd;
+    ctx->txid_salt = ((uint64_t)rd() << 32) ^ (uint64_t)rd();
+  } catch (...) {
+    const uint64_t now = (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
+    ctx->txid_salt = (now * 0x9E3779B97F4A7C15ull) ^ (uint64_t)reinterpret_cast<uintptr_t>(ctx);
+  }
   for (int k = 0; k < n_ids; ++k) ctx->tx_mu.emplace_back(new (std::nothrow) std::mutex());
   for (auto& m : ctx->tx_mu)
     if (!m) {
@@ -1605,6 +1624,237 @@ int hkv_verify_std_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_of
   uint32_t fault = 0;
   HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
   HKV_TRY(hipStreamSynchronize(c.st), "std txs sync");
+  if (fault & HKV_STATUS_TAIL_FAULT) {
+    g_last_hip = "multisig tail: work-queue wait timed out";
+    return c.done(HKV_E_INTERNAL);
+  }
+  return c.done();
+}
+
+// ---- in-batch prevouts: hkv_verify_block_txs ----------------------------------
+
+size_t hkv_txid_table_slots(size_t n_tx) { return n_tx < 0xFFFFFF00ull ? hkv::txid_table_slots(n_tx) : 0; }
+
+int hkv_debug_txid_hash_mask(hkv_ctx* ctx, int dev, uint32_t mask) {
+  if (!dev_ok(ctx, dev)) return HKV_E_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ctx->devs[(size_t)dev].txid_mask = mask;
+  return HKV_OK;
+}
+
+// a caller's table for n_tx txids: a power of two the kernels can index, no
+// smaller than the sizing rule's
+static bool table_ok(const uint8_t* txids, size_t n_tx, const uint32_t* table, size_t n_slots) {
+  return txids && table && aligned(txids, 16) && aligned(table, 4) && n_tx < 0xFFFFFF00ull &&
+         n_slots <= 0x80000000ull && (n_slots & (n_slots - 1)) == 0 && n_slots >= hkv::txid_table_slots(n_tx);
+}
+// (the launch-only forms read the device's mask without a lock, as they read
+// nothing else of the context: the hook is set between calls)
+static hkv::TxidTable txid_table(const hkv_ctx* ctx, int dev, const uint8_t* txids, size_t n_tx, uint32_t* table,
+                                 size_t n_slots) {
+  return hkv::TxidTable{reinterpret_cast<const uint32_t*>(txids), (uint32_t)n_tx, table, (uint32_t)n_slots,
+                        ctx->txid_salt, ctx->devs[(size_t)dev].txid_mask};
+}
+
+int hkv_txid_index_device(hkv_ctx* ctx, int dev, const uint8_t* d_txids, size_t n_tx, uint32_t* d_table,
+                          size_t n_slots, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !table_ok(d_txids, n_tx, d_table, n_slots)) return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  HKV_TRY(hkv::launch_txid_table(txid_table(ctx, dev, d_txids, n_tx, d_table, n_slots), c.st), "txid table launch");
+  return HKV_OK;
+}
+
+int hkv_txid_lookup_device(hkv_ctx* ctx, int dev, const uint8_t* d_txids, size_t n_tx, const uint32_t* d_table,
+                           size_t n_slots, const uint8_t* d_queries32, size_t n_q, uint32_t* d_found,
+                           void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !table_ok(d_txids, n_tx, d_table, n_slots) || n_q > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
+  if (n_q == 0) return HKV_OK;
+  if (!d_queries32 || !d_found || !aligned(d_found, 4)) return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  HKV_TRY(hkv::launch_txid_lookup(txid_table(ctx, dev, d_txids, n_tx, const_cast<uint32_t*>(d_table), n_slots),
+                                  d_queries32, (uint32_t)n_q, d_found, c.st),
+          "txid lookup launch");
+  return HKV_OK;
+}
+
+// The block entry points read every script through the tx bytes: the pool
+// follows them in one address range of less than 2^32 bytes. base: where the
+// pool starts, counted from bytes. It is also the only bound the device forms
+// have on the tx bytes (the verify's view ends at base + scripts_len, and an
+// in-batch reference lies below base), so a batch without a pool still names
+// where one would start: a null scripts pointer is refused.
+static bool block_pool_ok(const hkv_txs* t, uint32_t* base) {
+  *base = 0;
+  if (!t->scripts || t->scripts < t->bytes) return false;
+  const uint64_t b = (uint64_t)(t->scripts - t->bytes);
+  if (b + t->scripts_len > 0xFFFFFFFFull) return false;
+  *base = (uint32_t)b;
+  return true;
+}
+
+// txids, their table, the input counts and their scan (unless the caller ran
+// them: counted), then the block job builder, on st
+static int enqueue_block_jobs(hipStream_t st, const hkv_txs* dt, const hkv::StdPrevouts& p, uint32_t pool_base,
+                              size_t n_inputs, const hkv::TxidTable& tb, uint32_t* first, hkv_input_job* jobs,
+                              uint32_t* src, uint32_t* status, bool counted) {
+  HKV_TRY(hkv::launch_txids(dt->bytes, dt->offsets, dt->n_tx,
+                            reinterpret_cast<uint8_t*>(const_cast<uint32_t*>(tb.txids)), nullptr, st),
+          "txid launch");
+  HKV_TRY(hkv::launch_txid_table(tb, st), "txid table launch");
+  if (!counted)
+    HKV_TRY(hkv::launch_stdtx_counts(dt->bytes, dt->offsets, dt->n_tx, (uint32_t)n_inputs, first, status, st),
+            "input count launch");
+  HKV_TRY(hkv::launch_blocktx_jobs(dt->bytes, dt->offsets, dt->n_tx, first, p, pool_base, dt->scripts_len, tb,
+                                   (uint32_t)n_inputs, jobs, src, st),
+          "block job builder launch");
+  return HKV_OK;
+}
+
+int hkv_block_tx_jobs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                             const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                             const uint64_t* d_prev_values, size_t n_inputs, uint8_t* d_txids, uint32_t* d_table,
+                             size_t n_slots, uint32_t* d_input_first, hkv_input_job* d_jobs, uint32_t* d_input_src,
+                             uint32_t* d_status, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
+  if (d_txs->n_tx == 0) return HKV_OK;
+  uint32_t base;
+  if (!prevouts_ok(d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values) ||
+      !table_ok(d_txids, d_txs->n_tx, d_table, n_slots) || !block_pool_ok(d_txs, &base) || !d_input_first ||
+      !d_status || (n_inputs && (!d_jobs || !d_input_src)) || !aligned(d_input_first, 4) || !aligned(d_status, 4) ||
+      !aligned(d_jobs, 8) || !aligned(d_input_src, 4) || !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  return enqueue_block_jobs(c.st, d_txs,
+                            hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values}, base,
+                            n_inputs, txid_table(ctx, dev, d_txids, d_txs->n_tx, d_table, n_slots), d_input_first,
+                            d_jobs, d_input_src, d_status, false);
+}
+
+// the stages of hkv_verify_block_txs* on c's stream (the caller holds the Tx
+// lock and has acquired the scratch with status as the call's status word):
+// the block jobs, the unchanged per-input verify on the view that reads the
+// pool through the tx bytes, the per-tx reduction
+static int enqueue_verify_block_txs(Call& c, const hkv_txs* dt, const hkv::StdPrevouts& p, uint32_t pool_base,
+                                    int32_t forkid, size_t n_inputs, const hkv::TxidTable& tb, uint32_t* first,
+                                    hkv_input_job* jobs, uint32_t* src, void* recs, uint32_t* input_bits,
+                                    uint32_t* tx_bits, uint32_t* status, bool counted) {
+  HKV_RC(enqueue_block_jobs(c.st, dt, p, pool_base, n_inputs, tb, first, jobs, src, status, counted));
+  hkv_txs view = *dt;
+  view.scripts = dt->bytes;
+  view.scripts_len = pool_base + dt->scripts_len;
+  if (n_inputs) HKV_RC(enqueue_verify_std_inputs(c.d, &view, jobs, n_inputs, forkid, recs, input_bits, c.st));
+  HKV_TRY(hkv::launch_tx_verdicts(first, dt->n_tx, input_bits, status, tx_bits, c.st), "tx verdict launch");
+  return HKV_OK;
+}
+
+int hkv_verify_block_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                                const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                                const uint64_t* d_prev_values, int32_t forkid, size_t n_inputs, uint8_t* d_txids,
+                                uint32_t* d_table, size_t n_slots, uint32_t* d_input_first, hkv_input_job* d_jobs,
+                                uint32_t* d_input_src, void* d_records, uint32_t* d_input_bits, uint32_t* d_tx_bits,
+                                uint32_t* d_status, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
+  if (d_txs->n_tx == 0) return HKV_OK;
+  uint32_t base;
+  if (!prevouts_ok(d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values) ||
+      !table_ok(d_txids, d_txs->n_tx, d_table, n_slots) || !block_pool_ok(d_txs, &base) || !d_input_first ||
+      !d_tx_bits || !d_status || (n_inputs && (!d_jobs || !d_input_src || !d_records || !d_input_bits)) ||
+      !aligned(d_input_first, 4) || !aligned(d_status, 4) || !aligned(d_jobs, 8) || !aligned(d_input_src, 4) ||
+      !aligned(d_input_bits, 4) || !aligned(d_tx_bits, 4) || !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  const hkv::TxidTable tb = txid_table(ctx, dev, d_txids, d_txs->n_tx, d_table, n_slots);
+  Call c(ctx, dev, hip_stream, Lock::Tx);
+  int rc = c.acquire(d_status);
+  if (!rc)
+    rc = enqueue_verify_block_txs(c, d_txs,
+                                  hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values},
+                                  base, forkid, n_inputs, tb, d_input_first, d_jobs, d_input_src, d_records,
+                                  d_input_bits, d_tx_bits, d_status, false);
+  return c.done(rc);
+}
+
+int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                         const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                         int32_t forkid, uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
+                         size_t input_src_cap) {
+  if (!ctx || ctx->devs.empty() || !txs_ok(txs)) return HKV_E_ARG;
+  const size_t n_tx = txs->n_tx;
+  if (n_tx == 0) return HKV_OK;
+  if (!prev_offsets || !tx_verdict_bits || !tx_offsets_sorted(txs)) return HKV_E_ARG;
+  for (size_t t = 0; t < n_tx; ++t)
+    if (prev_offsets[t + 1] < prev_offsets[t]) return HKV_E_ARG;
+  const size_t e0 = prev_offsets[0], n_ent = prev_offsets[n_tx] - e0;
+  if (n_ent && (!prev_outpoints || !prev_scripts || !prev_values)) return HKV_E_ARG;
+  // the tx bytes, rounded up to 4, and the pool behind them in one buffer
+  const size_t nbytes = txs->offsets[n_tx], pool_at = round_up(nbytes, 4);
+  const size_t n_slots = hkv::txid_table_slots(n_tx);
+  if (pool_at + txs->scripts_len > 0xFFFFFFFFull || n_slots > 0x80000000ull) return HKV_E_ARG;
+  Call c(ctx, 0, Lock::Tx);
+  DevCtx& d = c.d;
+  uint32_t* status = reinterpret_cast<uint32_t*>(d.ms_bar + MS_HOST_STATUS);
+  // one staging buffer: values | entry offsets | script references | outpoints
+  // (the entries the offsets name, the offsets rebased by the first)
+  hkv::Layout l;
+  const size_t o_val = l.add(n_ent * 8, 8), o_off = l.add((n_tx + 1) * 4, 4), o_scr = l.add(n_ent * 8, 4),
+               o_op = l.add(n_ent * 36, 4);
+  std::vector<uint32_t> rebased(n_tx + 1);
+  for (size_t t = 0; t <= n_tx; ++t) rebased[t] = (uint32_t)(prev_offsets[t] - e0);
+  HKV_RC(c.acquire(status));
+  HKV_RC(d.stage_tx_bytes.reserve(pool_at + txs->scripts_len, "hipMalloc(tx bytes and pool)"));
+  HKV_RC(d.stage_tx_off.reserve(n_tx + 1, "hipMalloc(tx offsets)"));
+  HKV_RC(d.stage_prev.reserve(l.total, "hipMalloc(prevouts)"));
+  HKV_RC(d.std_first.reserve(n_tx + 1, "hipMalloc(input offsets)"));
+  HKV_RC(d.host_tx_bits.reserve((n_tx + 63) / 64 * 2, "hipMalloc(tx verdict words)"));
+  HKV_RC(d.blk_txids.reserve(n_tx * 32, "hipMalloc(txids)"));
+  HKV_RC(d.blk_table.reserve(n_slots, "hipMalloc(txid table)"));
+  uint8_t* tb_bytes = d.stage_tx_bytes;
+  if (nbytes) HKV_TRY(hipMemcpyAsync(tb_bytes, txs->bytes, nbytes, hipMemcpyHostToDevice, c.st), "H2D txs");
+  HKV_TRY(hipMemcpyAsync(d.stage_tx_off, txs->offsets, (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D offsets");
+  if (txs->scripts_len)
+    HKV_TRY(hipMemcpyAsync(tb_bytes + pool_at, txs->scripts, txs->scripts_len, hipMemcpyHostToDevice, c.st),
+            "H2D scripts");
+  const hkv_txs dt{tb_bytes, d.stage_tx_off, (uint32_t)n_tx, tb_bytes + pool_at, txs->scripts_len};
+  uint8_t* b = d.stage_prev;
+  const hkv::StdPrevouts p{reinterpret_cast<const uint32_t*>(b + o_off), b + o_op,
+                           reinterpret_cast<const uint32_t*>(b + o_scr),
+                           reinterpret_cast<const uint64_t*>(b + o_val)};
+  HKV_TRY(hipMemcpyAsync(b + o_off, rebased.data(), (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D prevout offsets");
+  if (n_ent) {
+    HKV_TRY(hipMemcpyAsync(b + o_op, prev_outpoints + e0 * 36, n_ent * 36, hipMemcpyHostToDevice, c.st),
+            "H2D prevout outpoints");
+    HKV_TRY(hipMemcpyAsync(b + o_scr, prev_scripts + e0 * 2, n_ent * 8, hipMemcpyHostToDevice, c.st),
+            "H2D prevout scripts");
+    HKV_TRY(hipMemcpyAsync(b + o_val, prev_values + e0, n_ent * 8, hipMemcpyHostToDevice, c.st), "H2D prevout values");
+  }
+  // the input total sizes the scratch: counted on the device, read back once
+  // (the count's own status bit is dropped: the total is not known before it)
+  uint32_t total = 0;
+  HKV_TRY(hkv::launch_stdtx_counts(dt.bytes, dt.offsets, dt.n_tx, 0, d.std_first, status, c.st), "input count launch");
+  HKV_TRY(hipMemcpyAsync(&total, d.std_first + n_tx, sizeof(total), hipMemcpyDeviceToHost, c.st), "D2H input total");
+  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
+  HKV_TRY(hipStreamSynchronize(c.st), "input count sync");
+  const size_t n = total;
+  if (n > HKV_MAX_STD_INPUTS || (input_src && n > input_src_cap)) return c.done(HKV_E_ARG);
+  HKV_RC(d.std_jobs.reserve(n, "hipMalloc(jobs)"));
+  HKV_RC(d.blk_src.reserve(n, "hipMalloc(input src)"));
+  HKV_RC(d.recs.reserve(n * hkv::REC_SIZE, "hipMalloc(records)"));
+  HKV_RC(d.host_std_bits.reserve((n + 63) / 64 * 2, "hipMalloc(verdict words)"));
+  const hkv::TxidTable tb{reinterpret_cast<const uint32_t*>(d.blk_txids.get()), (uint32_t)n_tx, d.blk_table,
+                          (uint32_t)n_slots, ctx->txid_salt, d.txid_mask};
+  HKV_RC(enqueue_verify_block_txs(c, &dt, p, (uint32_t)pool_at, forkid, n, tb, d.std_first, d.std_jobs, d.blk_src,
+                                  d.recs, d.host_std_bits, d.host_tx_bits, status, true));
+  // (the tx words come in pairs per 64 txs; the caller gets ceil(n_tx/32))
+  HKV_TRY(hipMemcpyAsync(tx_verdict_bits, d.host_tx_bits, (n_tx + 31) / 32 * 4, hipMemcpyDeviceToHost, c.st),
+          "D2H tx bits");
+  if (input_first)
+    HKV_TRY(hipMemcpyAsync(input_first, d.std_first, (n_tx + 1) * 4, hipMemcpyDeviceToHost, c.st), "D2H input offsets");
+  if (input_src && n) HKV_TRY(hipMemcpyAsync(input_src, d.blk_src, n * 4, hipMemcpyDeviceToHost, c.st), "D2H input src");
+  uint32_t fault = 0;
+  HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
+  HKV_TRY(hipStreamSynchronize(c.st), "block txs sync");
   if (fault & HKV_STATUS_TAIL_FAULT) {
     g_last_hip = "multisig tail: work-queue wait timed out";
     return c.done(HKV_E_INTERNAL);

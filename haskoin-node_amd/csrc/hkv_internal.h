@@ -227,6 +227,20 @@ hipError_t launch_stdtx_jobs(const uint8_t* txs, const uint32_t* tx_off, uint32_
 // words. status (or null): every bit is 0 once it holds HKV_STATUS_INPUT_COUNT
 hipError_t launch_tx_verdicts(const uint32_t* input_first, uint32_t n_tx, const uint32_t* input_bits,
                               const uint32_t* status, uint32_t* tx_bits, hipStream_t st);
+// hkv_blocktx.hip: in-batch prevouts from device-computed txids (hkv_blocktx.h
+// defines TxidTable: the txids, the slots, the salt and the debug mask).
+struct TxidTable;
+// the slots cleared to empty (a memset on st), then one insert per tx
+hipError_t launch_txid_table(const TxidTable& tb, hipStream_t st);
+// found[q] = the smallest tx index whose txid is queries[32q, 32q + 32), or 0xFFFFFFFF
+hipError_t launch_txid_lookup(const TxidTable& tb, const uint8_t* queries, uint32_t n_q, uint32_t* found,
+                              hipStream_t st);
+// launch_stdtx_jobs with the in-batch rule behind the list and one src word per
+// job. Script references count from txs: the caller's pool starts pool_base
+// bytes behind it and holds pool_len bytes.
+hipError_t launch_blocktx_jobs(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, const uint32_t* input_first,
+                               const StdPrevouts& p, uint32_t pool_base, uint32_t pool_len, const TxidTable& tb,
+                               uint32_t n_inputs, hkv_input_job* jobs, uint32_t* input_src, hipStream_t st);
 // hkv_headers.hip
 hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_limit, const uint8_t* prev0,
                           uint8_t* hashes, uint8_t* status, hipStream_t st);

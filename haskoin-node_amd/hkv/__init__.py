@@ -15,6 +15,9 @@ from .blocks import check_blocks, check_blocks_device, split_block, tx_ids, tx_i
 from .sighash import TxBatch, tx_sig_hash_batch, verify_std_inputs
 from .stdtx import (pack_prevouts, std_tx_jobs_device, tx_verdicts_device, verify_std_txs, verify_std_txs_detail,
                     verify_std_txs_device)
+from .blocktx import (HKV_SRC_LIST, HKV_SRC_NONE, block_layout, block_tx_jobs_device, debug_txid_hash_mask,
+                      txid_index_device, txid_lookup_device, txid_table_slots, verify_block_txs,
+                      verify_block_txs_detail, verify_block_txs_device, verify_block_txs_host)
 from .verify import (Verifier, VerifierConfig, verify_hash_sig_batch,
                      verify_raw_batch)
 from .actor import VerifyActor, VerifyActorConfig
@@ -29,5 +32,8 @@ __all__ = [
     "tx_ids", "tx_ids_device", "split_block", "check_blocks", "check_blocks_device",
     "verify_std_txs", "verify_std_txs_detail", "verify_std_txs_device", "std_tx_jobs_device", "tx_verdicts_device",
     "pack_prevouts",
+    "verify_block_txs", "verify_block_txs_host", "verify_block_txs_detail", "verify_block_txs_device",
+    "block_tx_jobs_device", "txid_index_device", "txid_lookup_device", "txid_table_slots", "block_layout",
+    "debug_txid_hash_mask", "HKV_SRC_LIST", "HKV_SRC_NONE",
     "HKV_TXID_OK", "HKV_TXID_BAD_TX", "HKV_BLK_MERKLE_OK", "HKV_BLK_MUTATED", "HKV_BLK_BAD_TX", "HKV_BLK_EMPTY",
 ]

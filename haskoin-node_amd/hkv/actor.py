@@ -19,6 +19,12 @@ a mailbox drained by one loop.
   verdicts and the tx verdict come from one ``verify_std_txs_detail`` call, so
   the caller numbers no inputs. It is its own call, in mailbox order; a failed
   call is re-submitted like any other, but there is no CPU fallback for it.
+* **Whole blocks.** ``verify_std_block`` posts a block's raw txs with, per tx,
+  the prevouts the caller's UTXO set has; inputs that spend outputs created
+  earlier in the block find them on the device (``verify_block_txs_detail``,
+  one call, in mailbox order, the retry policy of ``verify_std_tx``). It
+  publishes ``BlockVerified`` or ``BlockRejected`` with the failing (tx, input)
+  pairs; with ``skip_coinbase`` tx 0 is not judged.
 * **Errors.** A failed call (``HkvError``: HKV_E_INTERNAL when the call's
   multisig tail gave up, a device error) is re-submitted to the GPU up to
   ``retries`` times, then handed to ``fallback`` — in the Haskell actor,
@@ -40,6 +46,7 @@ from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 from .lib import HkvError
 from .sighash import verify_std_inputs
+from .blocktx import verify_block_txs_detail
 from .stdtx import verify_std_txs_detail
 
 # Outcomes published per message (VerifyEvent in the Haskell module).
@@ -92,6 +99,14 @@ class _StdTx:
     key: Any
     tx: bytes
     prevouts: Sequence[Tuple[bytes, bytes, int]]  # (36-byte wire outpoint, prevout scriptPubKey, value), any order
+
+
+@dataclass
+class _StdBlock:
+    key: Any
+    txs: Sequence[bytes]  # the block's txs in block order
+    prevouts: Sequence[Sequence[Tuple[bytes, bytes, int]]]  # per tx: the prevouts the caller has (its UTXO hits)
+    skip_coinbase: bool
 
 
 _STOP = object()
@@ -149,6 +164,20 @@ class VerifyActor:
         or one that does not parse)."""
         self._post(_StdTx(key, tx, list(prevouts)))
 
+    def verify_std_block(self, key, txs: Sequence[bytes], prevouts: Sequence[Sequence[Tuple[bytes, bytes, int]]],
+                         skip_coinbase: bool = True) -> None:
+        """verifyStdTx for every tx of a block, from the raw txs in block order
+        and, per tx, the prevouts the caller's UTXO set has: an input that
+        spends an output created earlier in the block finds it on the device
+        (``verify_block_txs_detail``). Publishes BlockVerified, or
+        BlockRejected with the (tx, input) pairs that fail or found no
+        prevout; a rejected tx without a failing input (it does not parse, or
+        has no inputs) is named as (tx, -1). With skip_coinbase tx 0 is not
+        judged (a coinbase has no prevout and verifyStdTx rejects it)."""
+        if len(prevouts) != len(txs):
+            raise ValueError("one prevout list per tx")
+        self._post(_StdBlock(key, list(txs), [list(p) for p in prevouts], skip_coinbase))
+
     def _post(self, msg) -> None:
         if self._crash is not None:
             raise RuntimeError("verify actor stopped on an error") from self._crash
@@ -189,6 +218,9 @@ class VerifyActor:
                     continue
                 if isinstance(msg, _StdTx):
                     self._handle_std_tx(msg)
+                    continue
+                if isinstance(msg, _StdBlock):
+                    self._handle_std_block(msg)
                     continue
                 batch, n = [msg], len(msg.inputs)
                 deadline = time.monotonic() + self.cfg.max_wait_s
@@ -247,6 +279,28 @@ class VerifyActor:
             self.stats.batch_inputs.append(len(per_input[0]))
             bad = tuple(i for i, v in enumerate(per_input[0]) if not v)
             self.publish(TxVerified(m.key) if ok[0] else TxRejected(m.key, bad))
+            return
+        self.publish(VerifyFailed(m.key, err))
+
+    def _handle_std_block(self, m: _StdBlock) -> None:
+        err = None
+        for _ in range(1 + self.cfg.retries):
+            self.stats.gpu_calls += 1
+            try:
+                ok, per_input, _ = verify_block_txs_detail(self.v, m.txs, m.prevouts, self.cfg.forkid)
+            except HkvError as e:
+                self.stats.gpu_failures += 1
+                err = str(e)
+                self.stats.errors.append(err)
+                continue
+            self.stats.batch_inputs.append(sum(len(p) for p in per_input))
+            bad = []
+            for t in range(1 if m.skip_coinbase else 0, len(m.txs)):
+                if ok[t]:
+                    continue
+                failing = [(t, i) for i, v in enumerate(per_input[t]) if not v]
+                bad += failing or [(t, -1)]
+            self.publish(BlockRejected(m.key, tuple(bad)) if bad else BlockVerified(m.key))
             return
         self.publish(VerifyFailed(m.key, err))
 

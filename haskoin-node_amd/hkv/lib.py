@@ -26,6 +26,7 @@ HKV_OK = 0
 HKV_FAIL_NONE, HKV_FAIL_ENQUEUE, HKV_FAIL_JOIN, HKV_FAIL_ALLOC, HKV_FAIL_TAIL = 0, 1, 2, 3, 4
 HKV_STATUS_TAIL_FAULT = 1
 HKV_STATUS_INPUT_COUNT = 2
+HKV_SRC_NONE, HKV_SRC_LIST = 0xFFFFFFFF, 0xFFFFFFFE
 _ERRS = {-1: "HKV_E_ARG", -2: "HKV_E_NODEV", -3: "HKV_E_OOM", -4: "HKV_E_HIP", -5: "HKV_E_INTERNAL"}
 
 _PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -111,6 +112,19 @@ EXPORTS = {
                                           c_void_p, c_void_p]),
     "hkv_verify_std_txs": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int32,
                                    POINTER(c_uint32)]),
+    "hkv_txid_table_slots": (c_size_t, [c_size_t]),
+    "hkv_txid_index_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "hkv_txid_lookup_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                       c_void_p, c_void_p]),
+    "hkv_block_tx_jobs_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "hkv_verify_block_txs_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
+                                            ctypes.c_int32, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hkv_verify_block_txs": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
+                                     ctypes.c_int32, POINTER(c_uint32), c_void_p, c_void_p, c_size_t]),
+    "hkv_debug_txid_hash_mask": (c_int, [c_void_p, c_int, c_uint32]),
     "hkv_merkle_roots": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "hkv_merkle_roots_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),

@@ -41,6 +41,15 @@
  *       matched input, one verdict per tx. hkv_std_tx_jobs_device is the
  *       matching alone (the prevout provider), hkv_tx_verdicts_device the
  *       per-tx `all`.
+ *   hkv_verify_block_txs / hkv_verify_block_txs_device
+ *       replaces the same N calls of `verifyStdTx` for the txs of whole blocks
+ *       and the host work in front of them: a prevout created earlier in the
+ *       same batch (which no UTXO provider has yet) is found on the device from
+ *       the device-computed `txHash`, where the caller of hkv_verify_std_txs
+ *       must parse and hash every tx, build a txid map and copy each parent
+ *       output into the prevout lists. hkv_block_tx_jobs_device is that
+ *       provider alone; hkv_txid_index_device / hkv_txid_lookup_device the
+ *       `HashMap TxHash Int` it stands on.
  *   hkv_check_headers / hkv_check_headers_device
  *       replaces the per-header part of haskoin-core `connectBlocks` reached
  *       from importHeaders (/root/reference/src/Haskoin/Node/Chain.hs:500-520):
@@ -524,6 +533,131 @@ int hkv_check_blocks(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* block_off
 int hkv_check_blocks_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_block_offsets,
                             size_t n_blocks, const uint8_t* d_headers, uint8_t* d_txids, uint8_t* d_scratch,
                             uint8_t* d_roots, uint8_t* d_mutated, uint8_t* d_status, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
+ * Batch verifyStdTx for whole blocks: prevouts created earlier in the batch.
+ *
+ * hkv_verify_std_txs* takes every prevout from the caller. A block input may
+ * spend an output created earlier in the same block, and during initial block
+ * download an output of an earlier block of the same batch; no UTXO provider
+ * has those yet. hkv_verify_block_txs* finds them itself. The caller hands
+ * over the raw txs in block order and, per tx, the prevouts it does have.
+ *
+ * For input i of a tx t that parses, whose outpoint is (h, k) as wire bytes:
+ *  1. The list first, unchanged. Tx t's own prevout list is consulted by the
+ *     matchTemplate rule above exactly as in hkv_verify_std_txs*. A hit gives
+ *     the entry's script reference and amount, and src = HKV_SRC_LIST.
+ *  2. Otherwise the batch. Let p be the smallest index u such that tx u parses
+ *     and txHash(tx u) == h, txHash being what hkv_tx_ids computes (digest
+ *     order, witness stripped, varints re-emitted canonically). Input i
+ *     resolves only if p exists, p < t, and k < the output count of tx p. It
+ *     then takes output k of tx p: the scriptPubKey bytes where they lie in
+ *     the transaction buffer, and the LE64 amount. src = p.
+ *  3. Otherwise nothing. src = HKV_SRC_NONE and the job keeps script_len = 0.
+ *     No template matches a zero-length script, so the input is false and so
+ *     is the transaction.
+ * Consequences:
+ *  - A transaction cannot spend a later transaction. It cannot spend itself.
+ *  - A parent that does not parse has an all-zero txid and is never indexed.
+ *    A coinbase input (32 zero bytes, index 0xFFFFFFFF) therefore finds
+ *    nothing, and its transaction is 0, as under verifyStdTx.
+ *  - Transactions with equal txids have equal outputs, so the choice of p
+ *    affects only src.
+ *  - Two inputs that take the same in-batch output both resolve. Double-spend
+ *    and UTXO accounting stay with the caller, which can do them from src and
+ *    the outpoint.
+ *  - A batch with all-empty lists is legal.
+ *  - A batch with no in-batch spends gives exactly the verdicts of
+ *    hkv_verify_std_txs*.
+ *
+ * Script references without copies. The per-input verify reads a prevout
+ * script as scripts + job.script_off. The device entry points below therefore
+ * require the script pool to follow the tx bytes in one address range:
+ * d_txs->scripts >= d_txs->bytes and (scripts - bytes) + scripts_len <=
+ * 0xFFFFFFFF (HKV_E_ARG otherwise), and the caller vouches that the pool
+ * starts at or after the end of the last tx, as it vouches for the offsets.
+ * scripts is also the only bound these entry points have on the tx bytes, so
+ * it is never NULL: a batch without a pool (all lists empty) passes
+ * scripts_len 0 and any scripts at or after the end of the last tx, e.g.
+ * bytes + offsets[n_tx] (HKV_E_ARG for NULL). The jobs they write count from d_txs->bytes:
+ * a list entry's reference is rebased by scripts - bytes, an in-batch
+ * reference is the offset of the output's script within the tx bytes, and the
+ * verify runs on the view {scripts = bytes, scripts_len = (scripts - bytes) +
+ * scripts_len}. A list entry whose (offset, length) overruns the caller's
+ * scripts_len gets script_off 0 and script_len 0 (its amount and
+ * src = HKV_SRC_LIST stay): the verdict such an entry has under
+ * hkv_verify_std_txs*. The host form takes any two host buffers and stages
+ * them so (the tx bytes rounded up to 4, then the pool).
+ *
+ * The walk to output k of a parent is O(parent inputs + k) dependent byte
+ * reads by the child's lane: a parent of 2,000 outputs with 2,000 children in
+ * the batch is about 4 M steps.
+ * ------------------------------------------------------------------------ */
+#define HKV_SRC_NONE 0xFFFFFFFFu /* the input found no prevout                  */
+#define HKV_SRC_LIST 0xFFFFFFFEu /* the prevout came from the tx's own list     */
+/* The txid table: open addressing over n_tx txids, uint32_t slots holding the
+ * smallest tx index of a txid, 0xFFFFFFFF when empty. This is the slot count
+ * for n_tx txids: the smallest power of two >= 2 * n_tx and >= 64 (0 for
+ * n_tx >= 0xFFFFFF00). Replaces sizing a `HashMap TxHash Int`. */
+size_t hkv_txid_table_slots(size_t n_tx);
+/* Build the table (replaces HashMap.fromListWith min (zip txids [0..])):
+ * d_txids n_tx * 32 bytes as hkv_tx_ids_device writes them, 16-byte aligned;
+ * d_table n_slots words, n_slots a power of two >= hkv_txid_table_slots(n_tx)
+ * and <= 2^31. All-zero txids are skipped. The slot hash is salted per
+ * context at hkv_open. Enqueued on hip_stream (a memset of the table, then
+ * one launch), not synchronised; stateless as hkv_tx_ids_device. */
+int hkv_txid_index_device(hkv_ctx* ctx, int dev, const uint8_t* d_txids, size_t n_tx, uint32_t* d_table,
+                          size_t n_slots, void* hip_stream);
+/* Look n_q 32-byte txids (any alignment) up in a table hkv_txid_index_device
+ * built from the same d_txids, n_tx and n_slots on this context (replaces n_q
+ * calls of HashMap.lookup): d_found[q] = the smallest tx index with that
+ * txid, or 0xFFFFFFFF. Enqueued, stateless. */
+int hkv_txid_lookup_device(hkv_ctx* ctx, int dev, const uint8_t* d_txids, size_t n_tx, const uint32_t* d_table,
+                           size_t n_slots, const uint8_t* d_queries32, size_t n_q, uint32_t* d_found,
+                           void* hip_stream);
+/* The prevout provider alone (replaces the caller's parse, txHash, txid map
+ * and output copy in front of verifyStdTx): hkv_tx_ids_device into d_txids,
+ * hkv_txid_index_device into d_table, the input counts and their prefix sums
+ * as hkv_std_tx_jobs_device, then one job and one src word per input by the
+ * rule above. Arguments as hkv_std_tx_jobs_device, plus d_txids (n_tx * 32
+ * bytes, 16-byte aligned), d_table / n_slots as above and d_input_src
+ * (n_inputs words: HKV_SRC_LIST, HKV_SRC_NONE or the parent's tx index;
+ * HKV_SRC_NONE in slots past the device's total). HKV_STATUS_INPUT_COUNT and
+ * the surplus slots behave as there. Enqueued, stateless: no context scratch,
+ * no lock. n_inputs <= 0xFFFFFF00. */
+int hkv_block_tx_jobs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                             const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                             const uint64_t* d_prev_values, size_t n_inputs, uint8_t* d_txids, uint32_t* d_table,
+                             size_t n_slots, uint32_t* d_input_first, hkv_input_job* d_jobs, uint32_t* d_input_src,
+                             uint32_t* d_status, void* hip_stream);
+/* Batch verifyStdTx with in-batch prevouts, on device (replaces N calls of
+ * verifyStdTx and the host work above): txids, table, count, scan, block jobs,
+ * the per-input verify on the view, the per-tx reduction, all enqueued on
+ * hip_stream with no host wait (ASYNCHRONOUS as hkv_verify_std_txs_device,
+ * whose arguments, scratch and status word it shares). d_txids,
+ * d_input_first, d_input_src and d_input_bits stay readable afterwards. */
+int hkv_verify_block_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                                const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                                const uint64_t* d_prev_values, int32_t forkid, size_t n_inputs, uint8_t* d_txids,
+                                uint32_t* d_table, size_t n_slots, uint32_t* d_input_first, hkv_input_job* d_jobs,
+                                uint32_t* d_input_src, void* d_records, uint32_t* d_input_bits, uint32_t* d_tx_bits,
+                                uint32_t* d_status, void* hip_stream);
+/* Host-memory form (replaces the same calls); writes ceil(n_tx/32) words of tx
+ * verdicts. First device, blocking, one readback of the input total as
+ * hkv_verify_std_txs. Optional outputs: input_first (n_tx + 1 words, or NULL)
+ * and input_src (or NULL; input_src_cap words of room: HKV_E_ARG when the
+ * batch holds more inputs; an input is at least 41 bytes of its tx). HKV_E_ARG
+ * for decreasing prev_offsets or tx offsets; HKV_E_INTERNAL on a multisig tail
+ * fault. */
+int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                         const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                         int32_t forkid, uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
+                         size_t input_src_cap);
+/* Test hook in the style of hkv_debug_ms_window (no reference counterpart):
+ * the slot hash of the txid table is ANDed with mask in device dev's later
+ * calls (default 0xFFFFFFFF). 0 sends every key to slot 0, the longest
+ * possible probe chain. Results do not depend on the mask or the salt. */
+int hkv_debug_txid_hash_mask(hkv_ctx* ctx, int dev, uint32_t mask);
 
 /* Synthetic-data hooks (block-mix generator, off the verify path):
  * n random private keys -> d_priv (n*32, big-endian), compressed public keys
