@@ -37,6 +37,9 @@ module Haskoin.Node.Verify
     verifyStdInputBatch,
     verifyStdTxBatch,
     verifyBlockTxBatch,
+    BlockSpends (..),
+    checkBlockTxBatch,
+    judgeBlockSpends,
     txHashBatch,
     BlockCheck (..),
     checkBlocksBatch,
@@ -277,8 +280,9 @@ verifyStdTxBatch v net xs = withMVar v.lock $ \_ -> do
 -- nothing for in-block spends. A coinbase finds nothing and is False, as under
 -- verifyStdTx: the caller skips element 0 of a block. The second component is
 -- per tx and input the source of its prevout: 'hkvSrcList', 'hkvSrcNone' or
--- the parent's index in the batch, from which the caller does its double-spend
--- and UTXO accounting.
+-- the parent's index in the batch. Double spends within the batch and the
+-- value balance come from 'checkBlockTxBatch'; spends against the UTXO set stay
+-- with the caller.
 verifyBlockTxBatch :: Verifier -> Network -> [(Tx, [(ScriptOutput, Word64, OutPoint)])] -> IO ([Bool], [[Word32]])
 verifyBlockTxBatch _ _ [] = return ([], [])
 verifyBlockTxBatch v net xs = withMVar v.lock $ \_ -> do
@@ -313,6 +317,99 @@ verifyBlockTxBatch v net xs = withMVar v.lock $ \_ -> do
                         first <- map fromIntegral <$> peekArray (n + 1) pfirst :: IO [Int]
                         srcs <- peekArray (last first) psrc
                         return (oks, [take (e - b) (drop b srcs) | (b, e) <- zip first (tail first)])
+
+-- | What 'checkBlockTxBatch' adds to 'verifyBlockTxBatch', per tx: for each
+-- input the (tx, input) of the first input of the batch that carries its
+-- outpoint (itself when it is the first), the exact input and output sums
+-- (@maxBound@ once an amount or a running sum exceeds the money bound) and the
+-- @hkvSpend*@ flag byte.
+data BlockSpends = BlockSpends
+  { verdicts :: ![Bool],
+    sources :: ![[Word32]],
+    spenders :: ![[(Int, Int)]],
+    sums :: ![(Word64, Word64)],
+    spendFlags :: ![Word8]
+  }
+
+-- | 'verifyBlockTxBatch' with the spend stage behind it on the GPU
+-- (@hkv_verify_block_txs_spends@): replaces the outpoint map and the amount
+-- sums a validator builds around 'verifyStdTx' when it connects a block. The
+-- money bound is the Network's @maxSatoshi@ (assumed name), passed in by the
+-- caller; it must be below 2^63.
+checkBlockTxBatch :: Verifier -> Network -> Word64 -> [(Tx, [(ScriptOutput, Word64, OutPoint)])] -> IO BlockSpends
+checkBlockTxBatch _ _ _ [] = return (BlockSpends [] [] [] [] [])
+checkBlockTxBatch v net maxMoney xs = withMVar v.lock $ \_ -> do
+  let raws = map (runPutS . serialize . fst) xs
+      offs = scanl (+) 0 (map (fromIntegral . B.length) raws) :: [Word32]
+      entries = concatMap snd xs
+      poffs = scanl (+) 0 (map (fromIntegral . length . snd) xs) :: [Word32]
+      scripts = map (\(so, _, _) -> encodeOutputBS so) entries
+      soffs = scanl (+) 0 (map (fromIntegral . B.length) scripts) :: [Word32]
+      srefs = concat [[o, fromIntegral (B.length s)] | (s, o) <- zip scripts soffs] :: [Word32]
+      vals = [val | (_, val, _) <- entries]
+      ops = B.concat [runPutS (serialize op) | (_, _, op) <- entries]
+      forkid = maybe hkvNoForkId fromIntegral (getSigHashForkId net)
+      n = length xs
+      nw = (n + 31) `div` 32
+      nin = sum (map (length . (.inputs) . fst) xs)
+  BU.unsafeUseAsCString (B.concat raws) $ \pbytes ->
+    BU.unsafeUseAsCString (B.concat scripts) $ \pscripts ->
+      BU.unsafeUseAsCString ops $ \pops ->
+        withArray offs $ \poffsets ->
+          withArray poffs $ \pprev ->
+            withArray srefs $ \psrefs ->
+              withArray vals $ \pvals ->
+                with (HkvTxs (castPtr pbytes) poffsets (fromIntegral n) (castPtr pscripts) (last soffs)) $ \ptxs ->
+                  allocaArray nw $ \bits ->
+                    allocaArray (n + 1) $ \pfirst ->
+                      allocaArray (max 1 nin) $ \psrc ->
+                        allocaArray (max 1 nin) $ \pspender ->
+                          allocaArray (2 * n) $ \psums ->
+                            allocaArray n $ \pflags -> do
+                              c_hkv_verify_block_txs_spends v.ctx ptxs pprev (castPtr pops) psrefs pvals forkid maxMoney
+                                bits pfirst psrc pspender (fromIntegral nin) psums pflags
+                                >>= check "hkv_verify_block_txs_spends" . fromIntegral
+                              oks <- readBits n bits
+                              first <- map fromIntegral <$> peekArray (n + 1) pfirst :: IO [Int]
+                              srcs <- peekArray (last first) psrc
+                              sps <- map fromIntegral <$> peekArray (last first) pspender :: IO [Int]
+                              sm <- peekArray (2 * n) psums
+                              fl <- peekArray n pflags
+                              let cut ys = [take (e - b) (drop b ys) | (b, e) <- zip first (tail first)]
+                                  -- the tx of input g: the last t with first[t] <= g
+                                  at g = let t = length (takeWhile (<= g) (tail first)) in (t, g - first !! t)
+                              return (BlockSpends oks (cut srcs) (cut (map at sps)) (pairs sm) fl)
+  where
+    pairs (a : b : rest) = (a, b) : pairs rest
+    pairs _ = []
+
+-- | The verdict of a block from 'checkBlockTxBatch', as the Python actor's
+-- @check_std_block@ publishes it: 'Nothing' when every judged tx has its
+-- verdict bit and @hkvSpendOk@ and (with @skipCoinbase@) tx 0 has the coinbase
+-- form and no later tx has it; otherwise the failing (tx, input) pairs (a tx
+-- without one is named as (tx, -1)), the double spends as (tx, input, first
+-- tx, first input) and the txs with every input resolved that lack
+-- @hkvSpendBalanced@.
+judgeBlockSpends :: Bool -> [[Bool]] -> BlockSpends -> Maybe ([(Int, Int)], [(Int, Int, Int, Int)], [Int])
+judgeBlockSpends skipCoinbase perInput r
+  | null bad && null twice && null short = Nothing
+  | otherwise = Just (bad, twice, short)
+  where
+    judged = drop (if skipCoinbase then 1 else 0) (zip3 [0 ..] r.verdicts r.spendFlags)
+    has f b = f .&. b /= 0
+    fine (_, ok, f) = ok && f .&. hkvSpendOk == hkvSpendOk && not (skipCoinbase && has f hkvSpendCoinbase)
+    rejected = filter (not . fine) judged
+    doubles t = [(t, i, ft, fi) | (i, (ft, fi)) <- zip [0 ..] (r.spenders !! t), (ft, fi) /= (t, i)]
+    isShort f = has f hkvSpendResolved && not (has f hkvSpendBalanced)
+    twice = concatMap (\(t, _, _) -> doubles t) rejected
+    short = [t | (t, _, f) <- rejected, isShort f]
+    bad =
+      [(0, -1) | skipCoinbase, (f : _) <- [r.spendFlags], not (has f hkvSpendCoinbase)]
+        ++ concat
+          [ if null failing && null (doubles t) && not (isShort f) then [(t, -1)] else failing
+            | (t, _, f) <- rejected,
+              let failing = [(t, i) | (i, False) <- zip [0 ..] (perInput !! t)]
+          ]
 
 -- | The serialised txs of a batch as an @hkv_txs@ without a script pool:
 -- each tx's @runPutS . serialize@ back to back, offsets as prefix sums.
@@ -408,6 +505,9 @@ data VerifyConfig = VerifyConfig
 data VerifyEvent
   = BlockVerified !BlockHash
   | BlockRejected !BlockHash ![(Int, Int)]
+  | -- | 'judgeBlockSpends' on a 'checkBlockTxBatch' result: failing inputs,
+    -- double spends (tx, input, first tx, first input), unbalanced txs
+    BlockSpendRejected !BlockHash ![(Int, Int)] ![(Int, Int, Int, Int)] ![Int]
   | TxVerified !TxHash
   | TxRejected !TxHash ![Int]
 

@@ -25,8 +25,16 @@ module Haskoin.Node.Verify.FFI
     c_hkv_verify_std_inputs,
     c_hkv_verify_std_txs,
     c_hkv_verify_block_txs,
+    c_hkv_verify_block_txs_spends,
     hkvSrcNone,
     hkvSrcList,
+    hkvSpendResolved,
+    hkvSpendFirst,
+    hkvSpendInRange,
+    hkvSpendOutRange,
+    hkvSpendBalanced,
+    hkvSpendCoinbase,
+    hkvSpendOk,
     c_hkv_verify_std_inputs_device_status,
     c_hkv_device_fault,
     c_hkv_device_healthy,
@@ -143,6 +151,22 @@ hkvSrcNone, hkvSrcList :: Word32
 hkvSrcNone = 0xFFFFFFFF
 hkvSrcList = 0xFFFFFFFE
 
+-- | HKV_SPEND_* flags of hkv_verify_block_txs_spends' per-tx flag byte.
+hkvSpendResolved, hkvSpendFirst, hkvSpendInRange, hkvSpendOutRange, hkvSpendBalanced, hkvSpendCoinbase, hkvSpendOk :: Word8
+hkvSpendResolved = 0x01 -- every input found a prevout
+
+hkvSpendFirst = 0x02 -- no input's outpoint is carried by an earlier input of the batch
+
+hkvSpendInRange = 0x04 -- every input amount and their sum <= max_money
+
+hkvSpendOutRange = 0x08 -- every output amount and their sum <= max_money
+
+hkvSpendBalanced = 0x10 -- resolved, both in range, inputs >= outputs
+
+hkvSpendCoinbase = 0x20 -- exactly one input, with the null outpoint
+
+hkvSpendOk = 0x1F -- the first five
+
 -- | HKV_TXID_BAD_TX: the per-tx status of a tx that does not parse (its txid
 -- is 32 zero bytes).
 hkvTxidBadTx :: Word8
@@ -202,6 +226,17 @@ foreign import ccall safe "hkv_verify_block_txs"
   c_hkv_verify_block_txs ::
     Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word32 -> Ptr Word8 -> Ptr Word32 -> Ptr Word64 -> Int32 -> Ptr Word32 ->
     Ptr Word32 -> Ptr Word32 -> CSize -> IO CInt
+
+-- hkv_verify_block_txs with the spend stage behind it: the same arguments with
+-- max_money (the Network's maxSatoshi, below 2^63) after the fork id, then
+-- input_spender (per input: the index of the first input of the batch with its
+-- outpoint; or nullPtr) before the room both per-input outputs have, tx_sums
+-- (2 * n_tx words: input sum, output sum; or nullPtr) and tx_flags (n_tx bytes
+-- of hkvSpend* flags).
+foreign import ccall safe "hkv_verify_block_txs_spends"
+  c_hkv_verify_block_txs_spends ::
+    Ptr HkvCtx -> Ptr HkvTxs -> Ptr Word32 -> Ptr Word8 -> Ptr Word32 -> Ptr Word64 -> Int32 -> Word64 -> Ptr Word32 ->
+    Ptr Word32 -> Ptr Word32 -> Ptr Word32 -> CSize -> Ptr Word64 -> Ptr Word8 -> IO CInt
 
 -- The asynchronous block path: everything is enqueued on the caller's HIP
 -- stream (the last argument); d_status gets HKV_STATUS_* bits ORed in on it.

@@ -22,6 +22,7 @@
 
 #include "../../include/hkv.h"
 #include "hkv_blocktx.h"
+#include "hkv_spends.h"
 #include "hkv_internal.h"
 #include "hkv_launch_plan.h"
 #include "hkv_layout.h"
@@ -143,6 +144,12 @@ struct DevCtx {
   DevBuf<uint8_t> blk_txids;
   DevBuf<uint32_t> blk_table, blk_src;
   uint32_t txid_mask = 0xFFFFFFFFu;  // hkv_debug_txid_hash_mask: ANDed into the slot hash of later calls
+  // the host form of the spend stage (hkv_verify_block_txs_spends): the outpoint
+  // offsets, the spent-outpoint table, the spender words, the sums, the flags
+  DevBuf<uint32_t> spd_off, spd_table, spd_spender;
+  DevBuf<uint64_t> spd_sums;
+  DevBuf<uint8_t> spd_flags;
+  uint32_t spend_stages = hkv::SPEND_STAGE_ALL;  // hkv_debug_spend_stages: the launches later calls run
   // multisig inputs (hkv_sighash.hip section 4, hkv_kernels.hip 2e): desc
   // words, offsets, candidate and key-check verdict words, the candidate then
   // the key records; the host form's verdict words
@@ -711,7 +718,7 @@ class Call {
 
 extern "C" {
 
-uint32_t hkv_version(void) { return (1u << 16) | 3u; }
+uint32_t hkv_version(void) { return (1u << 16) | 4u; }
 
 const char* hkv_strerror(int err) {
   switch (err) {
@@ -1776,10 +1783,22 @@ int hkv_verify_block_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, con
   return c.done(rc);
 }
 
-int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
-                         const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
-                         int32_t forkid, uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
-                         size_t input_src_cap) {
+// what the host form of the spend stage adds to hkv_verify_block_txs' outputs
+struct HostSpends {
+  uint64_t max_money;
+  uint32_t* input_spender;  // or null
+  uint64_t* tx_sums;        // or null
+  uint8_t* tx_flags;
+};
+
+// hkv_verify_block_txs, and with sp its spend stage behind it on the same
+// stream (hkv_verify_block_txs_spends): one staging, one readback of the input
+// total, one final wait
+static int verify_block_txs_host(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                                 const uint8_t* prev_outpoints, const uint32_t* prev_scripts,
+                                 const uint64_t* prev_values, int32_t forkid, uint32_t* tx_verdict_bits,
+                                 uint32_t* input_first, uint32_t* input_src, size_t input_src_cap,
+                                 const HostSpends* sp) {
   if (!ctx || ctx->devs.empty() || !txs_ok(txs)) return HKV_E_ARG;
   const size_t n_tx = txs->n_tx;
   if (n_tx == 0) return HKV_OK;
@@ -1837,7 +1856,17 @@ int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_
   HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
   HKV_TRY(hipStreamSynchronize(c.st), "input count sync");
   const size_t n = total;
-  if (n > HKV_MAX_STD_INPUTS || (input_src && n > input_src_cap)) return c.done(HKV_E_ARG);
+  if (n > HKV_MAX_STD_INPUTS || ((input_src || (sp && sp->input_spender)) && n > input_src_cap))
+    return c.done(HKV_E_ARG);
+  const size_t spend_slots = sp ? hkv::spend_table_slots(n) : 0;
+  if (sp) {
+    if (spend_slots == 0) return c.done(HKV_E_ARG);
+    HKV_RC(d.spd_off.reserve(n, "hipMalloc(outpoint offsets)"));
+    HKV_RC(d.spd_table.reserve(spend_slots, "hipMalloc(spend table)"));
+    HKV_RC(d.spd_spender.reserve(n, "hipMalloc(input spender)"));
+    HKV_RC(d.spd_sums.reserve(2 * n_tx, "hipMalloc(tx sums)"));
+    HKV_RC(d.spd_flags.reserve(n_tx, "hipMalloc(tx flags)"));
+  }
   HKV_RC(d.std_jobs.reserve(n, "hipMalloc(jobs)"));
   HKV_RC(d.blk_src.reserve(n, "hipMalloc(input src)"));
   HKV_RC(d.recs.reserve(n * hkv::REC_SIZE, "hipMalloc(records)"));
@@ -1852,6 +1881,17 @@ int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_
   if (input_first)
     HKV_TRY(hipMemcpyAsync(input_first, d.std_first, (n_tx + 1) * 4, hipMemcpyDeviceToHost, c.st), "D2H input offsets");
   if (input_src && n) HKV_TRY(hipMemcpyAsync(input_src, d.blk_src, n * 4, hipMemcpyDeviceToHost, c.st), "D2H input src");
+  if (sp) {
+    const hkv::SpendStage stage{dt.bytes,      dt.offsets,  dt.n_tx,     d.std_first,   d.std_jobs,
+                                d.blk_src,     (uint32_t)n, sp->max_money, d.spd_off,   d.spd_table,
+                                (uint32_t)spend_slots, ctx->txid_salt, d.txid_mask, d.spd_spender, d.spd_sums,
+                                d.spd_flags,   status};
+    HKV_TRY(hkv::launch_block_spends(stage, hkv::SPEND_STAGE_ALL, c.st), "spend stage launch");
+    if (sp->input_spender && n)
+      HKV_TRY(hipMemcpyAsync(sp->input_spender, d.spd_spender, n * 4, hipMemcpyDeviceToHost, c.st), "D2H input spender");
+    if (sp->tx_sums) HKV_TRY(hipMemcpyAsync(sp->tx_sums, d.spd_sums, 2 * n_tx * 8, hipMemcpyDeviceToHost, c.st), "D2H tx sums");
+    HKV_TRY(hipMemcpyAsync(sp->tx_flags, d.spd_flags, n_tx, hipMemcpyDeviceToHost, c.st), "D2H tx flags");
+  }
   uint32_t fault = 0;
   HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
   HKV_TRY(hipStreamSynchronize(c.st), "block txs sync");
@@ -1860,6 +1900,65 @@ int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_
     return c.done(HKV_E_INTERNAL);
   }
   return c.done();
+}
+
+int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                         const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                         int32_t forkid, uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
+                         size_t input_src_cap) {
+  return verify_block_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid,
+                               tx_verdict_bits, input_first, input_src, input_src_cap, nullptr);
+}
+
+// ---- whole-block spend checks: hkv_block_spends_device -------------------------
+
+size_t hkv_spend_table_slots(size_t n_inputs) { return hkv::spend_table_slots(n_inputs); }
+
+int hkv_debug_spend_stages(hkv_ctx* ctx, int dev, uint32_t stages) {
+  if (!dev_ok(ctx, dev)) return HKV_E_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ctx->devs[(size_t)dev].spend_stages = stages & hkv::SPEND_STAGE_ALL;
+  return HKV_OK;
+}
+
+int hkv_block_spends_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_input_first,
+                            const hkv_input_job* d_jobs, const uint32_t* d_input_src, size_t n_inputs,
+                            uint64_t max_money, uint32_t* d_input_off, uint32_t* d_table, size_t n_slots,
+                            uint32_t* d_input_spender, uint64_t* d_tx_sums, uint8_t* d_tx_flags, uint32_t* d_status,
+                            void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS || max_money >= hkv::SPEND_MONEY_LIMIT)
+    return HKV_E_ARG;
+  const size_t need = hkv::spend_table_slots(n_inputs);
+  if (need == 0 || n_slots < need || n_slots > hkv::SPEND_MAX_SLOTS || (n_slots & (n_slots - 1)) != 0) return HKV_E_ARG;
+  if (d_txs->n_tx == 0) return HKV_OK;
+  if (!d_input_first || !d_tx_sums || !d_tx_flags || !d_status ||
+      (n_inputs && (!d_jobs || !d_input_src || !d_input_off || !d_table || !d_input_spender)) ||
+      !aligned(d_input_first, 4) || !aligned(d_jobs, 8) || !aligned(d_input_src, 4) || !aligned(d_input_off, 4) ||
+      !aligned(d_table, 4) || !aligned(d_input_spender, 4) || !aligned(d_tx_sums, 8) || !aligned(d_status, 4) ||
+      !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  // (the salt, the mask and the stage hook are read without a lock, as the
+  // launch-only block forms read the mask: the hooks are set between calls)
+  const DevCtx& d = ctx->devs[(size_t)dev];
+  const hkv::SpendStage stage{d_txs->bytes, d_txs->offsets, d_txs->n_tx,       d_input_first,  d_jobs,
+                              d_input_src,  (uint32_t)n_inputs, max_money,     d_input_off,    d_table,
+                              (uint32_t)n_slots, ctx->txid_salt, d.txid_mask,  d_input_spender, d_tx_sums,
+                              d_tx_flags,   d_status};
+  HKV_TRY(hkv::launch_block_spends(stage, d.spend_stages, c.st), "spend stage launch");
+  return HKV_OK;
+}
+
+int hkv_verify_block_txs_spends(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                                const uint8_t* prev_outpoints, const uint32_t* prev_scripts,
+                                const uint64_t* prev_values, int32_t forkid, uint64_t max_money,
+                                uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
+                                uint32_t* input_spender, size_t input_cap, uint64_t* tx_sums, uint8_t* tx_flags) {
+  if (!tx_flags || max_money >= hkv::SPEND_MONEY_LIMIT) return HKV_E_ARG;
+  const HostSpends sp{max_money, input_spender, tx_sums, tx_flags};
+  return verify_block_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid,
+                               tx_verdict_bits, input_first, input_src, input_cap, &sp);
 }
 
 }  // extern "C"

@@ -241,6 +241,33 @@ hipError_t launch_txid_lookup(const TxidTable& tb, const uint8_t* queries, uint3
 hipError_t launch_blocktx_jobs(const uint8_t* txs, const uint32_t* tx_off, uint32_t n_tx, const uint32_t* input_first,
                                const StdPrevouts& p, uint32_t pool_base, uint32_t pool_len, const TxidTable& tb,
                                uint32_t n_inputs, hkv_input_job* jobs, uint32_t* input_src, hipStream_t st);
+// hkv_spends.hip: the first spender of every outpoint and the per-tx value
+// balance (hkv_spends.h states the rule), on what the block call left in HBM.
+struct SpendStage {
+  const uint8_t* txs;
+  const uint32_t* tx_off;
+  uint32_t n_tx;
+  const uint32_t* input_first;
+  const hkv_input_job* jobs;
+  const uint32_t* input_src;
+  uint32_t n_inputs;  // the caller's total: the capacity of every per-input array
+  uint64_t max_money;
+  uint32_t* input_off;
+  uint32_t* slots;
+  uint32_t n_slots;
+  uint64_t salt;
+  uint32_t mask;
+  uint32_t* spender;
+  uint64_t* tx_sums;
+  uint8_t* tx_flags;
+  uint32_t* status;
+};
+// the four launches, in stream order (hkv_debug_spend_stages: a bench leaves some out)
+constexpr uint32_t SPEND_STAGE_WALK = 1u, SPEND_STAGE_TABLE = 2u, SPEND_STAGE_SPENDER = 4u, SPEND_STAGE_FOLD = 8u,
+                   SPEND_STAGE_ALL = 15u;
+// the walk, the table (a memset on st, then one insert per input), the
+// spender lookup and the fold; with n_inputs == 0 only the two per-tx launches
+hipError_t launch_block_spends(const SpendStage& s, uint32_t stages, hipStream_t st);
 // hkv_headers.hip
 hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_limit, const uint8_t* prev0,
                           uint8_t* hashes, uint8_t* status, hipStream_t st);

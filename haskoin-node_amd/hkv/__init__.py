@@ -18,6 +18,9 @@ from .stdtx import (pack_prevouts, std_tx_jobs_device, tx_verdicts_device, verif
 from .blocktx import (HKV_SRC_LIST, HKV_SRC_NONE, block_layout, block_tx_jobs_device, debug_txid_hash_mask,
                       txid_index_device, txid_lookup_device, txid_table_slots, verify_block_txs,
                       verify_block_txs_detail, verify_block_txs_device, verify_block_txs_host)
+from .spends import (HKV_SPEND_BALANCED, HKV_SPEND_COINBASE, HKV_SPEND_FIRST, HKV_SPEND_IN_RANGE, HKV_SPEND_OK,
+                     HKV_SPEND_OUT_RANGE, HKV_SPEND_RESOLVED, block_spends_device, check_block_txs,
+                     debug_spend_stages, spend_table_slots, verify_block_txs_spends_host)
 from .verify import (Verifier, VerifierConfig, verify_hash_sig_batch,
                      verify_raw_batch)
 from .actor import VerifyActor, VerifyActorConfig
@@ -35,5 +38,8 @@ __all__ = [
     "verify_block_txs", "verify_block_txs_host", "verify_block_txs_detail", "verify_block_txs_device",
     "block_tx_jobs_device", "txid_index_device", "txid_lookup_device", "txid_table_slots", "block_layout",
     "debug_txid_hash_mask", "HKV_SRC_LIST", "HKV_SRC_NONE",
+    "spend_table_slots", "block_spends_device", "verify_block_txs_spends_host", "check_block_txs",
+    "debug_spend_stages", "HKV_SPEND_RESOLVED", "HKV_SPEND_FIRST", "HKV_SPEND_IN_RANGE", "HKV_SPEND_OUT_RANGE",
+    "HKV_SPEND_BALANCED", "HKV_SPEND_COINBASE", "HKV_SPEND_OK",
     "HKV_TXID_OK", "HKV_TXID_BAD_TX", "HKV_BLK_MERKLE_OK", "HKV_BLK_MUTATED", "HKV_BLK_BAD_TX", "HKV_BLK_EMPTY",
 ]

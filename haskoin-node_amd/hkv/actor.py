@@ -25,6 +25,13 @@ a mailbox drained by one loop.
   one call, in mailbox order, the retry policy of ``verify_std_tx``). It
   publishes ``BlockVerified`` or ``BlockRejected`` with the failing (tx, input)
   pairs; with ``skip_coinbase`` tx 0 is not judged.
+* **Whole blocks with their spends.** ``check_std_block`` is
+  ``verify_std_block`` with the spend stage behind the signature verdicts
+  (``check_block_txs``, one call, the same retry policy): an outpoint spent
+  twice within the block and a tx that pays out more than it takes in (or an
+  amount beyond ``max_money``) reject the block. It publishes ``BlockVerified``
+  or ``BlockSpendRejected`` with the failing inputs, the double spends and the
+  unbalanced txs; ``verify_std_block`` itself looks at signatures only.
 * **Errors.** A failed call (``HkvError``: HKV_E_INTERNAL when the call's
   multisig tail gave up, a device error) is re-submitted to the GPU up to
   ``retries`` times, then handed to ``fallback`` — in the Haskell actor,
@@ -44,9 +51,10 @@ import time
 from dataclasses import dataclass, field
 from typing import Any, Callable, List, Optional, Sequence, Tuple
 
-from .lib import HkvError
+from .lib import HKV_SPEND_BALANCED, HKV_SPEND_COINBASE, HKV_SPEND_OK, HKV_SPEND_RESOLVED, HkvError
 from .sighash import verify_std_inputs
 from .blocktx import verify_block_txs_detail
+from .spends import check_block_txs
 from .stdtx import verify_std_txs_detail
 
 # Outcomes published per message (VerifyEvent in the Haskell module).
@@ -61,6 +69,15 @@ class BlockVerified:
 class BlockRejected:
     key: Any
     bad: Tuple[Tuple[int, int], ...]  # (tx index, input index) of each failing input
+
+
+@dataclass(frozen=True)
+class BlockSpendRejected:
+    key: Any
+    bad: Tuple[Tuple[int, int], ...]  # as BlockRejected.bad
+    # (tx, input, first tx, first input): the input's outpoint was already spent by (first tx, first input)
+    double_spent: Tuple[Tuple[int, int, int, int], ...]
+    unbalanced: Tuple[int, ...]  # txs whose resolved inputs do not cover their outputs within max_money
 
 
 @dataclass(frozen=True)
@@ -106,6 +123,15 @@ class _StdBlock:
     key: Any
     txs: Sequence[bytes]  # the block's txs in block order
     prevouts: Sequence[Sequence[Tuple[bytes, bytes, int]]]  # per tx: the prevouts the caller has (its UTXO hits)
+    skip_coinbase: bool
+
+
+@dataclass
+class _CheckBlock:
+    key: Any
+    txs: Sequence[bytes]
+    prevouts: Sequence[Sequence[Tuple[bytes, bytes, int]]]
+    max_money: int
     skip_coinbase: bool
 
 
@@ -178,6 +204,23 @@ class VerifyActor:
             raise ValueError("one prevout list per tx")
         self._post(_StdBlock(key, list(txs), [list(p) for p in prevouts], skip_coinbase))
 
+    def check_std_block(self, key, txs: Sequence[bytes], prevouts: Sequence[Sequence[Tuple[bytes, bytes, int]]],
+                        max_money: int, skip_coinbase: bool = True) -> None:
+        """verify_std_block plus the block's spends (``check_block_txs``, one
+        call): publishes BlockVerified when every judged tx has its verdict
+        bit and HKV_SPEND_OK (every input resolved and the first spender of
+        its outpoint in the block, amounts within max_money, inputs >=
+        outputs) and, with skip_coinbase, tx 0 has the coinbase form and no
+        later tx has it. Otherwise BlockSpendRejected: ``bad`` as
+        BlockRejected's (a tx 0 that is no coinbase, under skip_coinbase, is
+        named as (0, -1)), ``double_spent`` the inputs whose outpoint an
+        earlier input of the block carries, with that input, ``unbalanced``
+        the txs with every input resolved that still lack HKV_SPEND_BALANCED.
+        With skip_coinbase tx 0 is not judged otherwise."""
+        if len(prevouts) != len(txs):
+            raise ValueError("one prevout list per tx")
+        self._post(_CheckBlock(key, list(txs), [list(p) for p in prevouts], int(max_money), skip_coinbase))
+
     def _post(self, msg) -> None:
         if self._crash is not None:
             raise RuntimeError("verify actor stopped on an error") from self._crash
@@ -221,6 +264,9 @@ class VerifyActor:
                     continue
                 if isinstance(msg, _StdBlock):
                     self._handle_std_block(msg)
+                    continue
+                if isinstance(msg, _CheckBlock):
+                    self._handle_check_block(msg)
                     continue
                 batch, n = [msg], len(msg.inputs)
                 deadline = time.monotonic() + self.cfg.max_wait_s
@@ -304,6 +350,42 @@ class VerifyActor:
             return
         self.publish(VerifyFailed(m.key, err))
 
+    def _handle_check_block(self, m: _CheckBlock) -> None:
+        err = None
+        for _ in range(1 + self.cfg.retries):
+            self.stats.gpu_calls += 1
+            try:
+                ok, per_input, _, spender, _, flags = check_block_txs(self.v, m.txs, m.prevouts, self.cfg.forkid,
+                                                                      m.max_money)
+            except HkvError as e:
+                self.stats.gpu_failures += 1
+                err = str(e)
+                self.stats.errors.append(err)
+                continue
+            self.stats.batch_inputs.append(sum(len(p) for p in per_input))
+            bad, double_spent, unbalanced = [], [], []
+            if m.skip_coinbase and m.txs and not flags[0] & HKV_SPEND_COINBASE:
+                bad.append((0, -1))
+            for t in range(1 if m.skip_coinbase else 0, len(m.txs)):
+                if ok[t] and flags[t] & HKV_SPEND_OK == HKV_SPEND_OK and not (
+                        m.skip_coinbase and flags[t] & HKV_SPEND_COINBASE):
+                    continue
+                failing = [(t, i) for i, v in enumerate(per_input[t]) if not v]
+                twice = [(t, i) + first for i, first in enumerate(spender[t]) if first != (t, i)]
+                short = bool(flags[t] & HKV_SPEND_RESOLVED) and not flags[t] & HKV_SPEND_BALANCED
+                double_spent += twice
+                if short:
+                    unbalanced.append(t)
+                # (a rejected tx that none of the three names: it does not parse, has no inputs,
+                # or is a second coinbase)
+                bad += failing or ([] if twice or short else [(t, -1)])
+            if bad or double_spent or unbalanced:
+                self.publish(BlockSpendRejected(m.key, tuple(bad), tuple(double_spent), tuple(unbalanced)))
+            else:
+                self.publish(BlockVerified(m.key))
+            return
+        self.publish(VerifyFailed(m.key, err))
+
     def _handle_block(self, m: _Block) -> None:
         ok, err = self._verify(m.txs, m.inputs) if m.inputs else ([], None)
         if ok is None:
@@ -327,5 +409,5 @@ class VerifyActor:
             self.publish(TxRejected(m.key, bad) if bad else TxVerified(m.key))
 
 
-__all__ = ["VerifyActor", "VerifyActorConfig", "ActorStats", "BlockVerified", "BlockRejected", "TxVerified",
-           "TxRejected", "VerifyFailed"]
+__all__ = ["VerifyActor", "VerifyActorConfig", "ActorStats", "BlockVerified", "BlockRejected", "BlockSpendRejected",
+           "TxVerified", "TxRejected", "VerifyFailed"]

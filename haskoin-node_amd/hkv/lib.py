@@ -27,6 +27,8 @@ HKV_FAIL_NONE, HKV_FAIL_ENQUEUE, HKV_FAIL_JOIN, HKV_FAIL_ALLOC, HKV_FAIL_TAIL = 
 HKV_STATUS_TAIL_FAULT = 1
 HKV_STATUS_INPUT_COUNT = 2
 HKV_SRC_NONE, HKV_SRC_LIST = 0xFFFFFFFF, 0xFFFFFFFE
+HKV_SPEND_RESOLVED, HKV_SPEND_FIRST, HKV_SPEND_IN_RANGE, HKV_SPEND_OUT_RANGE = 0x01, 0x02, 0x04, 0x08
+HKV_SPEND_BALANCED, HKV_SPEND_COINBASE, HKV_SPEND_OK = 0x10, 0x20, 0x1F
 _ERRS = {-1: "HKV_E_ARG", -2: "HKV_E_NODEV", -3: "HKV_E_OOM", -4: "HKV_E_HIP", -5: "HKV_E_INTERNAL"}
 
 _PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -125,6 +127,14 @@ EXPORTS = {
     "hkv_verify_block_txs": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
                                      ctypes.c_int32, POINTER(c_uint32), c_void_p, c_void_p, c_size_t]),
     "hkv_debug_txid_hash_mask": (c_int, [c_void_p, c_int, c_uint32]),
+    "hkv_spend_table_slots": (c_size_t, [c_size_t]),
+    "hkv_block_spends_device": (c_int, [c_void_p, c_int, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_uint64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "hkv_verify_block_txs_spends": (c_int, [c_void_p, POINTER(HkvTxs), c_void_p, c_void_p, c_void_p, c_void_p,
+                                            ctypes.c_int32, c_uint64, POINTER(c_uint32), c_void_p, c_void_p,
+                                            c_void_p, c_size_t, c_void_p, c_void_p]),
+    "hkv_debug_spend_stages": (c_int, [c_void_p, c_int, c_uint32]),
     "hkv_merkle_roots": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "hkv_merkle_roots_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),

@@ -50,6 +50,12 @@
  *       output into the prevout lists. hkv_block_tx_jobs_device is that
  *       provider alone; hkv_txid_index_device / hkv_txid_lookup_device the
  *       `HashMap TxHash Int` it stands on.
+ *   hkv_block_spends_device / hkv_verify_block_txs_spends
+ *       replaces the host work a validator does around `verifyStdTx` when it
+ *       connects a block: the outpoints of every input in a `HashMap OutPoint`
+ *       (a second spender of an outpoint within the batch is a double spend)
+ *       and the sums of input and output amounts against `maxSatoshi`, from
+ *       what hkv_verify_block_txs* leaves on the device.
  *   hkv_check_headers / hkv_check_headers_device
  *       replaces the per-header part of haskoin-core `connectBlocks` reached
  *       from importHeaders (/root/reference/src/Haskoin/Node/Chain.hs:500-520):
@@ -563,9 +569,11 @@ int hkv_check_blocks_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const u
  *    nothing, and its transaction is 0, as under verifyStdTx.
  *  - Transactions with equal txids have equal outputs, so the choice of p
  *    affects only src.
- *  - Two inputs that take the same in-batch output both resolve. Double-spend
- *    and UTXO accounting stay with the caller, which can do them from src and
- *    the outpoint.
+ *  - Two inputs that take the same in-batch output both resolve: this call
+ *    gives signature verdicts only. Double spends within the batch and each
+ *    tx's value balance are what hkv_block_spends_device (below) adds, on the
+ *    arrays this call leaves in HBM; spends against the caller's UTXO set
+ *    stay with the caller.
  *  - A batch with all-empty lists is legal.
  *  - A batch with no in-batch spends gives exactly the verdicts of
  *    hkv_verify_std_txs*.
@@ -656,8 +664,123 @@ int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_
 /* Test hook in the style of hkv_debug_ms_window (no reference counterpart):
  * the slot hash of the txid table is ANDed with mask in device dev's later
  * calls (default 0xFFFFFFFF). 0 sends every key to slot 0, the longest
- * possible probe chain. Results do not depend on the mask or the salt. */
+ * possible probe chain. The same mask is ANDed into the slot hash of the
+ * spent-outpoint table of hkv_block_spends_device. Results do not depend on
+ * the mask or the salt. */
 int hkv_debug_txid_hash_mask(hkv_ctx* ctx, int dev, uint32_t mask);
+
+/* ---------------------------------------------------------------------------
+ * Whole-block spend checks: double spends within the batch and value balance.
+ *
+ * hkv_verify_block_txs* delivers one signature verdict per tx. A block in
+ * which a tx is simply repeated (the copy spends the same outputs again and
+ * every signature still verifies) and a block whose txs pay out more than
+ * they take in both pass it. This stage adds what a validator does around
+ * verifyStdTx when it connects a block (parse every tx for its outpoints, a
+ * `HashMap OutPoint` of the spent ones, the sums of the input and output
+ * amounts against the Network's maxSatoshi), on the arrays the block call
+ * leaves in HBM. There is no haskoin-core function of this name.
+ *
+ * Inputs are numbered as everywhere else: input i of tx t is
+ * g = d_input_first[t] + i; a tx that does not parse has no inputs.
+ *
+ * Per input g, the first spender:
+ *  - spender[g] is the smallest g' whose 36-byte wire outpoint equals input
+ *    g's. It may be g itself.
+ *  - The comparison is on bytes only. Whether either input resolved does not
+ *    matter. Duplicates inside one tx count like duplicates across txs.
+ *  - The null outpoint (32 zero bytes, index 0xFFFFFFFF) is never indexed.
+ *    Such an input has spender[g] = g, so the coinbases of several blocks in
+ *    one batch do not conflict.
+ *  - Slots past the device's input total get 0xFFFFFFFF.
+ *
+ * Per tx t with at least one input, one flag byte and two sums, with
+ * in[g] = d_jobs[g].value (the amount the block call resolved) and the
+ * outputs' LE64 amounts read from the wire bytes:
+ *   HKV_SPEND_RESOLVED   every input has d_input_src[g] != HKV_SRC_NONE
+ *   HKV_SPEND_FIRST      every input has spender[g] == g
+ *   HKV_SPEND_IN_RANGE   every in[g] <= max_money and their exact sum
+ *                        <= max_money
+ *   HKV_SPEND_OUT_RANGE  every output amount <= max_money and their exact sum
+ *                        <= max_money (a tx with no outputs has sum 0, in
+ *                        range)
+ *   HKV_SPEND_BALANCED   RESOLVED, IN_RANGE, OUT_RANGE and in_sum >= out_sum
+ *                        (equality is balanced: fee 0)
+ *   HKV_SPEND_COINBASE   exactly one input, and its outpoint is null
+ *   HKV_SPEND_OK         the first five
+ *  - tx_sums[2t] is in_sum and tx_sums[2t + 1] is out_sum.
+ *  - Each sum is exact when its RANGE flag is set, and UINT64_MAX otherwise.
+ *  - A tx with no inputs (it does not parse, or it has none) gets flags 0 and
+ *    sums 0.
+ *  - max_money must be below 2^63 (HKV_E_ARG otherwise), so a running sum
+ *    that is still in range cannot wrap when one in-range amount is added.
+ *    Once either bound is exceeded, the sum sticks at out of range.
+ *
+ * Count mismatch: the stage checks d_input_first[n_tx] against the caller's
+ * n_inputs itself, and honours HKV_STATUS_INPUT_COUNT if the provider already
+ * set it in the same status word. On a mismatch it ORs the bit in; every tx
+ * flag byte is then 0, every sum is 0, nothing is written past n_inputs slots
+ * of any per-input array, and no read leaves the arrays.
+ *
+ * The first spender comes from an open-addressing table over the batch's
+ * inputs as the txid table above: uint32_t slots holding the smallest input
+ * index of one outpoint, 0xFFFFFFFF when empty, the slot hash salted per
+ * context and mixed with the outpoint's index. One lane walks one tx and
+ * folds one tx's inputs: a tx of 100,000 inputs is one lane's serial chain.
+ * ------------------------------------------------------------------------ */
+#define HKV_SPEND_RESOLVED 0x01u
+#define HKV_SPEND_FIRST 0x02u
+#define HKV_SPEND_IN_RANGE 0x04u
+#define HKV_SPEND_OUT_RANGE 0x08u
+#define HKV_SPEND_BALANCED 0x10u
+#define HKV_SPEND_COINBASE 0x20u
+#define HKV_SPEND_OK 0x1Fu
+/* The slot count of the spent-outpoint table for n_inputs inputs: the smallest
+ * power of two >= 2 * n_inputs and >= 64, and 0 when that would exceed 2^31
+ * (n_inputs > 2^30). Replaces sizing a `HashMap OutPoint Int`. */
+size_t hkv_spend_table_slots(size_t n_inputs);
+/* The spend stage on device (replaces the caller's parse for outpoints, its
+ * HashMap.fromListWith min (zip outpoints [0..]) and its amount sums). It runs
+ * after hkv_block_tx_jobs_device or hkv_verify_block_txs_device on the same
+ * stream, on the arrays those leave readable: d_txs, d_input_first
+ * (n_tx + 1 words), d_jobs (n_inputs jobs, of which the value is read),
+ * d_input_src (n_inputs words), with the same n_inputs and the same d_status.
+ * Scratch: d_input_off (n_inputs words: each input's outpoint offset, counted
+ * from d_txs->bytes; stays readable) and d_table (n_slots words, n_slots a
+ * power of two within [hkv_spend_table_slots(n_inputs), 2^31]). Out:
+ * d_input_spender (n_inputs words), d_tx_sums (2 * n_tx words, 8-byte
+ * aligned), d_tx_flags (n_tx bytes), HKV_STATUS_* ORed into d_status. Four
+ * launches and a memset of the table on hip_stream, enqueued and not
+ * synchronised; stateless and without a lock as hkv_block_tx_jobs_device: of
+ * the context it reads only the salt and the debug mask. HKV_E_ARG for a NULL
+ * or misaligned pointer, max_money >= 2^63, n_inputs > 0xFFFFFF00 and an
+ * n_slots outside that range. HKV_OK for n_tx == 0, with nothing launched;
+ * with n_inputs == 0 only the two per-tx launches run (and the per-input
+ * pointers may be NULL). */
+int hkv_block_spends_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_input_first,
+                            const hkv_input_job* d_jobs, const uint32_t* d_input_src, size_t n_inputs,
+                            uint64_t max_money, uint32_t* d_input_off, uint32_t* d_table, size_t n_slots,
+                            uint32_t* d_input_spender, uint64_t* d_tx_sums, uint8_t* d_tx_flags, uint32_t* d_status,
+                            void* hip_stream);
+/* Host-memory form: hkv_verify_block_txs, then the spend stage on the same
+ * stream, with the one readback of the input total that call has, then the
+ * extra copies back. Arguments as there, plus max_money, input_spender
+ * (or NULL), tx_sums (2 * n_tx words, or NULL) and tx_flags (n_tx bytes, not
+ * NULL). input_cap is the room of input_src and of input_spender, in words:
+ * HKV_E_ARG when either is given and the batch holds more inputs.
+ * tx_verdict_bits, input_first and input_src come out bit for bit as from
+ * hkv_verify_block_txs. First device, blocking. */
+int hkv_verify_block_txs_spends(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                                const uint8_t* prev_outpoints, const uint32_t* prev_scripts,
+                                const uint64_t* prev_values, int32_t forkid, uint64_t max_money,
+                                uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
+                                uint32_t* input_spender, size_t input_cap, uint64_t* tx_sums, uint8_t* tx_flags);
+/* Measurement hook (no reference counterpart): device dev's later
+ * hkv_block_spends_device calls run only the launches named in stages (bit 0
+ * the walk, bit 1 the table's memset and inserts, bit 2 the spender lookup,
+ * bit 3 the per-tx fold; default 15), so a bench can time each on arrays a
+ * full call filled before. Results of a partial call mean nothing. */
+int hkv_debug_spend_stages(hkv_ctx* ctx, int dev, uint32_t stages);
 
 /* Synthetic-data hooks (block-mix generator, off the verify path):
  * n random private keys -> d_priv (n*32, big-endian), compressed public keys
