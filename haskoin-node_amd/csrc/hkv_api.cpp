@@ -122,6 +122,11 @@ struct DevCtx {
   // caller's stream by these two events
   hipStream_t hash_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // the odd parts of a table / chain batch in two slots run here beside the
+  // even ones on the caller's stream (enqueue_table_chain), forked after the
+  // prologue and joined back after the last part by these two events
+  hipStream_t pipe_stream = nullptr;
+  hipEvent_t ev_pipe_fork = nullptr, ev_pipe_join = nullptr;
   DevBuf<uint32_t> gtab, qs;  // (qs: the largest plan's qs_quads so far, the resident grid's at least)
   DevBuf<uint32_t> im;    // IM_WORDS per signature of the largest n_pad
   DevBuf<uint32_t> bits;  // verdict words
@@ -167,8 +172,10 @@ struct DevCtx {
   bool inject_tail = false;          // hkv_debug_fail_device(HKV_FAIL_TAIL): the next tail's phase waits give up
   uint32_t* call_status = nullptr;   // the current call's status word (device; HKV_STATUS_* ORed in), or null: set by Call
   bool ms_dirty = false;             // a call failed after its scan launch: zero ms_ctr before the next scan
-  DevBuf<uint32_t> rare_ctr;         // y-free rare-lane count (hkv_finish_kernel appends, hkv_yverdict_kernel re-arms)
-  bool rare_dirty = false;           // a finish launch failed part-way: zero rare_ctr before the next one
+  // y-free rare-lane counts, a word per finish window (one, or a part each:
+  // hkv_finish_kernel appends, hkv_yverdict_kernel re-arms)
+  DevBuf<uint32_t> rare_ctr;
+  bool rare_dirty = false;           // a finish launch failed part-way, or rare_ctr grew: zero it before the next one
   DevBuf<uint32_t> aux;  // split launches: waves 4-5's A = u1 G, y0 and flags for the in-kernel join (AUX_WORDS each)
   // optional per-kernel timing (hkv_profile_*): events on the launch stream
   bool profile = false;
@@ -229,6 +236,7 @@ constexpr size_t MS_CAND_PER_INPUT = hkv::MS_CAND_PER_INPUT, MS_KEYS_PER_INPUT =
 // (HKV_MS_WIN_CAND / HKV_MS_WIN_KEYS, the windows' budget: hkv_tail_plan.h)
 constexpr size_t HKV_MAX_STD_INPUTS = 0xFFFFFF00ull;
 constexpr size_t MS_BAR_WORDS = 32, MS_FAULT = 16, MS_HOST_STATUS = 17;  // DevCtx::ms_bar
+constexpr size_t RARE_CTR_WORDS = HKV_MAX_STD_INPUTS / ((HKV_REC_PART) != 0 ? (HKV_REC_PART) : HKV_MAX_STD_INPUTS) + 1;  // DevCtx::rare_ctr at open
 #ifndef HKV_HOST_FIRST_DIV  // the host-batch path's first chunk: one resident grid / this
 #define HKV_HOST_FIRST_DIV 4
 #endif
@@ -279,6 +287,94 @@ int profile_mark(DevCtx& d, hipEvent_t (&e)[3], int k, hipStream_t st) {
   return HKV_OK;
 }
 
+// The rare-lane counts are re-armed by the verdict launches. A call that
+// failed between a finish and its verdict launch leaves them dirty, and a
+// grown block holds anything: both are zeroed on the stream before the next
+// finish launch.
+int ensure_rare(DevCtx& d, size_t count) {
+  if (d.rare_ctr.get() != nullptr && d.rare_ctr.size() >= count) return HKV_OK;
+  d.rare_dirty = true;
+  return d.rare_ctr.reserve(count, "hipMalloc(rare counters)");
+}
+int rearm_rare(DevCtx& d, hipStream_t st) {
+  if (!d.rare_dirty) return HKV_OK;
+  HKV_TRY(hipMemsetAsync(d.rare_ctr, 0, d.rare_ctr.size() * sizeof(uint32_t), st), "hipMemset(rare counters)");
+  d.rare_dirty = false;
+  return HKV_OK;
+}
+
+// The ecmult stage of a batch above half the resident grid (hkv_kernels.hip
+// 2a, 2b), after the whole-batch prologue on st: each part of the plan runs
+// its table and chain launches, then the finish, rare and verdict launches.
+// One slot: the parts are the plan's chunks, one after another on st, and the
+// finish launches take the batch as one window once the last chain has run.
+// Two slots: part k runs all five launches over its own window on stream
+// part_stream(k) — st or the pipe stream, forked here and joined back into st
+// before this returns, on every path — in slot part_slot(k) of qs, so the
+// table, finish and verdict launches of one part fill the issue slots the
+// other part's chain launch leaves, and the device does not drain between
+// launches. late_join: see enqueue_verify; every stream waits for it before
+// its first finish launch.
+int enqueue_table_chain(DevCtx& d, const hkv::RecPlan& plan, const hkv::RecOps& ops, hipEvent_t late_join,
+                        const void* late_recs, hipStream_t st) {
+  const bool piped = plan.qs_slots == 2;
+  const hipStream_t streams[2] = {st, d.pipe_stream};
+  HKV_RC(rearm_rare(d, st));
+  if (piped) {
+    HKV_TRY(hipEventRecord(d.ev_pipe_fork, st), "hipEventRecord(pipe fork)");
+    HKV_TRY(hipStreamWaitEvent(d.pipe_stream, d.ev_pipe_fork, 0), "hipStreamWaitEvent(pipe fork)");
+  }
+  hipError_t err = hipSuccess;
+  const char* what = nullptr;
+  bool slot_order = true;
+  uint32_t slot_user[2] = {0, 0};  // the stream of the slot's last chain launch
+  bool late_joined[2] = {late_join == nullptr, late_join == nullptr};
+  for (uint32_t k = 0; k < plan.n_parts; ++k) {
+    const uint32_t lane = piped ? hkv::RecPlan::part_stream(k) : 0u, slot = piped ? hkv::RecPlan::part_slot(k) : 0u;
+    const hipStream_t s = streams[lane];
+    // the table launch overwrites the slot: it must follow the slot's last
+    // chain launch, which alternating streams and slots give by stream order
+    if (k >= 2 && slot_user[slot] != lane) {
+      slot_order = false;
+      break;
+    }
+    slot_user[slot] = lane;
+    err = hkv::launch_table_chain(plan, ops, k, s);
+    if (err != hipSuccess) {
+      what = "ecmult launch";
+      break;
+    }
+    if (!piped) continue;
+    if (!late_joined[lane]) err = hipStreamWaitEvent(s, late_join, 0);
+    late_joined[lane] = true;
+    if (err == hipSuccess) err = hkv::launch_finish(plan, ops, plan.part(k), d.rare_ctr + k, late_recs, s);
+    if (err != hipSuccess) {
+      what = "finish launch";
+      break;
+    }
+  }
+  if (piped) {
+    // (joined whatever happened: a later call on any stream orders after st)
+    hipError_t e = hipEventRecord(d.ev_pipe_join, d.pipe_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, d.ev_pipe_join, 0);
+    if (err == hipSuccess && e != hipSuccess) err = e, what = "pipe join";
+  } else if (err == hipSuccess && slot_order) {
+    if (late_join != nullptr) err = hipStreamWaitEvent(st, late_join, 0);
+    if (err == hipSuccess) err = hkv::launch_finish(plan, ops, hkv::RecChunk{0, plan.n_pad}, d.rare_ctr, late_recs, st);
+    what = "finish launch";
+  }
+  if (!slot_order) {
+    d.rare_dirty = true;
+    g_last_hip = "a part's table launch is not ordered after its slot's last chain launch";
+    return HKV_E_INTERNAL;
+  }
+  if (err != hipSuccess) {
+    d.rare_dirty = true;
+    return hip_fail(err, what);
+  }
+  return HKV_OK;
+}
+
 // enqueue the verify of n records at d_records; verdict words in out_bits
 // ((n + 31) / 32 words, device memory) or, when null, in d.bits.
 // late_join (full-grid batches of standard inputs only): the event after
@@ -300,24 +396,25 @@ int enqueue_verify(DevCtx& d, const void* d_records, size_t n, uint32_t mode, hi
   HKV_RC(profile_mark(d, e, 0, st));
   if (std_pro != nullptr && plan.shape != hkv::Shape::Mid) return HKV_E_INTERNAL;  // (the lane prologue is a mid-size form)
   if (plan.aux) HKV_RC(ensure_aux(d, plan.n_pad));
+  if (plan.prologue) HKV_RC(ensure_rare(d, plan.qs_slots == 2 ? plan.n_parts : 1));  // (a word per finish window)
   // (operands taken after the reserves above, which may move the scratch)
   const hkv::RecOps ops{d.im, (uint32_t)n, d.gtab, d.qs, out_bits ? out_bits : d.bits.get(),
                         (uint32_t)(out_bits ? (n + 31) / 32 : plan.n_pad / 32), d.profile ? d.clk.get() : nullptr,
                         d.aux, d_records, mode};
   if (plan.prologue && std_pro == nullptr) HKV_TRY(hkv::launch_prologue(plan, ops, st), "prologue launch");
   HKV_RC(profile_mark(d, e, 1, st));
+  const void* late_recs = late_join != nullptr ? d_records : nullptr;
+  if (plan.shape == hkv::Shape::TableChain) {
+    HKV_RC(enqueue_table_chain(d, plan, ops, late_join, late_recs, st));
+    return profile_mark(d, e, 2, st);
+  }
   HKV_TRY(hkv::launch_ecmult(plan, ops, std_pro, st), "ecmult launch");
-  // full-grid batches: the finish kernels add u1 * G and decide x(R) == r
-  // through y_c = num / den (hkv_kernels.hip §2b). The rare-lane count is
-  // re-armed by the verdict kernel; a call that failed between the finish
-  // and verdict launches leaves it dirty, so it is zeroed on the stream first.
+  // mid-size batches: the finish kernels add u1 * G and decide x(R) == r
+  // through y_c = num / den (hkv_kernels.hip §2b), the batch as one window
   if (plan.prologue) {
     if (late_join != nullptr) HKV_TRY(hipStreamWaitEvent(st, late_join, 0), "hipStreamWaitEvent(hash join)");
-    if (d.rare_dirty) {
-      HKV_TRY(hipMemsetAsync(d.rare_ctr, 0, sizeof(uint32_t), st), "hipMemset(rare counter)");
-      d.rare_dirty = false;
-    }
-    const hipError_t e2 = hkv::launch_finish(plan, ops, d.rare_ctr, late_join != nullptr ? d_records : nullptr, st);
+    HKV_RC(rearm_rare(d, st));
+    const hipError_t e2 = hkv::launch_finish(plan, ops, hkv::RecChunk{0, plan.n_pad}, d.rare_ctr, late_recs, st);
     if (e2 != hipSuccess) {
       d.rare_dirty = true;
       return hip_fail(e2, "finish launch");
@@ -342,6 +439,17 @@ int init_device(DevCtx& d, int device) {
   HKV_TRY(hipStreamCreateWithFlags(&d.hash_stream, hipStreamNonBlocking), "hipStreamCreate(hash)");
   HKV_TRY(hipEventCreateWithFlags(&d.ev_fork, hipEventDisableTiming), "hipEventCreate(fork)");
   HKV_TRY(hipEventCreateWithFlags(&d.ev_join, hipEventDisableTiming), "hipEventCreate(join)");
+  // The pipe stream takes the highest stream priority. Streams of one
+  // priority share a small pool of hardware queues (4 by default), and a
+  // process with more streams than that (this context's four, the caller's,
+  // the null stream) may find the pipe stream on the caller's queue, where
+  // the two run one after the other (measured: profiles/r13_rec_pipeline/
+  // timeline_p4_one_queue.txt); another priority draws from another pool.
+  int prio_least = 0, prio_greatest = 0;
+  HKV_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest), "stream priority range");
+  HKV_TRY(hipStreamCreateWithPriority(&d.pipe_stream, hipStreamNonBlocking, prio_greatest), "hipStreamCreate(pipe)");
+  HKV_TRY(hipEventCreateWithFlags(&d.ev_pipe_fork, hipEventDisableTiming), "hipEventCreate(pipe fork)");
+  HKV_TRY(hipEventCreateWithFlags(&d.ev_pipe_join, hipEventDisableTiming), "hipEventCreate(pipe join)");
   HKV_TRY(hipEventCreateWithFlags(&d.last_use, hipEventDisableTiming), "hipEventCreate(scratch)");
   HKV_TRY(hipEventRecord(d.last_use, d.stream), "hipEventRecord(scratch)");
   // the multisig scan's two parity sums; the tail's queue words
@@ -349,8 +457,10 @@ int init_device(DevCtx& d, int device) {
   HKV_TRY(hipMemsetAsync(d.ms_ctr, 0, 4 * sizeof(uint64_t), d.stream), "hipMemset(multisig counters)");
   HKV_RC(d.ms_bar.reserve(MS_BAR_WORDS, "hipMalloc(multisig barrier)"));
   HKV_TRY(hipMemsetAsync(d.ms_bar, 0, MS_BAR_WORDS * sizeof(unsigned int), d.stream), "hipMemset(multisig barrier)");
-  HKV_RC(d.rare_ctr.reserve(1, "hipMalloc(rare counter)"));
-  HKV_TRY(hipMemsetAsync(d.rare_ctr, 0, sizeof(uint32_t), d.stream), "hipMemset(rare counter)");
+  // (a word per part of the largest batch at the default part length, so
+  // that only a test's shorter parts ever grow it)
+  HKV_RC(d.rare_ctr.reserve(RARE_CTR_WORDS, "hipMalloc(rare counters)"));
+  HKV_TRY(hipMemsetAsync(d.rare_ctr, 0, RARE_CTR_WORDS * sizeof(uint32_t), d.stream), "hipMemset(rare counters)");
   HKV_TRY(hipStreamSynchronize(d.stream), "multisig counters sync");  // callers may use other streams
   HKV_TRY(hipDeviceGetAttribute(&d.wall_khz, hipDeviceAttributeWallClockRate, device), "wall clock rate");
   HKV_RC(d.clk.reserve(CLK_WORDS, "hipMalloc(clock probe)"));
@@ -379,6 +489,13 @@ int init_device(DevCtx& d, int device) {
     const unsigned long long c = std::strtoull(e, nullptr, 10) / hkv::WG * hkv::WG;
     if (c >= (unsigned long long)hkv::WG && c <= HKV_REC_CHUNK) g.rec_chunk = (size_t)c;
   }
+  // the parts of a chunk (test hook: two, three with a short last one, the
+  // shortest; 0 turns them off); the plan rounds it up to PART_ALIGN
+  g.rec_part = HKV_REC_PART;
+  if (const char* e = std::getenv("HKV_REC_PART")) {
+    const unsigned long long c = std::strtoull(e, nullptr, 10);
+    if (c <= HKV_REC_CHUNK) g.rec_part = (size_t)c;
+  }
   // (the resident grid's Q tables: the smallest batch's plan)
   HKV_RC(d.qs.reserve(hkv::plan_records(g, 1).qs_quads * 4, "hipMalloc(qtab scratch)"));
   HKV_TRY(hkv::launch_gtable(d.gtab, d.stream), "gtable launch");
@@ -397,9 +514,9 @@ void free_device(DevCtx& d) {
   if (d.stream) (void)hipStreamSynchronize(d.stream);
   (void)hipDeviceSynchronize();
   clear_events(d);
-  for (hipEvent_t e : {d.last_use, d.ev_fork, d.ev_join})
+  for (hipEvent_t e : {d.last_use, d.ev_fork, d.ev_join, d.ev_pipe_fork, d.ev_pipe_join})
     if (e) (void)hipEventDestroy(e);
-  for (hipStream_t s : {d.stream, d.copy_stream, d.hash_stream})
+  for (hipStream_t s : {d.stream, d.copy_stream, d.hash_stream, d.pipe_stream})
     if (s) (void)hipStreamDestroy(s);
   d = DevCtx();  // (its buffers free themselves)
 }
@@ -853,6 +970,14 @@ int hkv_debug_launch_shape(hkv_ctx* ctx, int dev, uint32_t kind, size_t n, uint3
     out[1] = (p.scan_in_kernel ? 1u : 0u) | (p.rows_in_kernel ? 2u : 0u) | (p.overlap ? 4u : 0u);
     out[2] = (uint32_t)first, out[3] = (uint32_t)((n + chunk - 1) / chunk);
   }
+  return HKV_OK;
+}
+
+int hkv_debug_rec_parts(hkv_ctx* ctx, int dev, size_t n, uint32_t* part_len, uint32_t* n_parts) {
+  if (!dev_ok(ctx, dev) || n == 0 || n > HKV_MAX_STD_INPUTS || !part_len || !n_parts) return HKV_E_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  const hkv::RecPlan p = hkv::plan_records(ctx->devs[(size_t)dev].geo, n);
+  *part_len = p.part_len, *n_parts = p.n_parts;
   return HKV_OK;
 }
 

@@ -107,6 +107,9 @@ hipError_t launch_prologue(const RecPlan& p, const RecOps& r, hipStream_t st);
 // (the overlapped path) — std_parse, prologue, s^-1 and GLV in one lane per
 // input at the head of the mid-size ecmult kernel's lanes
 hipError_t launch_ecmult(const RecPlan& p, const RecOps& r, const StdOps* std_pro, hipStream_t st);
+// TableChain, which launch_ecmult does not run: the table and chain launches
+// of plan.part(k), in the part's slot of qs
+hipError_t launch_table_chain(const RecPlan& p, const RecOps& r, uint32_t k, hipStream_t st);
 hipError_t launch_gtable(uint32_t* gtab, hipStream_t st);
 // the multisig scan operands a fused launch may take over (hkv_ms_scan_kernel's);
 // counters: this call's running sum (candidates | key checks << 32), one of
@@ -174,10 +177,12 @@ struct StdOps {
 hipError_t launch_std_verify_split(const StdPlan& p, const StdOps& o, const RecOps& r, const MsScan* ms,
                                    const uint32_t* tx_off, hipStream_t st);
 // y-free full-grid batches (Mid: the paired-product instance; TableChain):
-// u1 * G, the y0 = num / den reduction and the verdict bitmap
-// (plan.verdict_stride lanes). late_recs: large standard-input batches, u1
-// and the validity from the final records first
-hipError_t launch_finish(const RecPlan& p, const RecOps& r, uint32_t* rare_ctr, const void* late_recs,
+// u1 * G, the y0 = num / den reduction and the verdict bitmap over the window
+// w of the batch — all of it, or one part of a two-slot plan — on
+// verdict_stride_of(w.cn) lanes. rare_ctr: the window's own rare-lane count
+// (zero on entry, re-armed by the verdict launch). late_recs: large
+// standard-input batches, u1 and the validity from the final records first
+hipError_t launch_finish(const RecPlan& p, const RecOps& r, RecChunk w, uint32_t* rare_ctr, const void* late_recs,
                          hipStream_t st);
 hipError_t launch_gen_pool(uint64_t seed, uint32_t npool, uint32_t* pool, hipStream_t st);
 hipError_t launch_gen_records(uint64_t seed, uint64_t index0, uint32_t n, const uint32_t* pool, uint32_t npool,

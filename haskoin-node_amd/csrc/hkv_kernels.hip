@@ -787,14 +787,18 @@ __global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict_
 //     launches, one signature per lane at 4 waves per SIMD, over chunks of cn
 //     signatures (i0 .. i0 + cn, cn a multiple of WG). Signature s of the
 //     chunk owns table slot s of qs and the Zg slot behind the chunk's tables
-//     (hkv_layout.h HKV_REC_CHUNK). The table launch is bound by memory (it
-//     streams 2.4 KB per signature), the chain launch by VALU issue. A 1M
+//     (hkv_layout.h HKV_REC_CHUNK). The chain launch is bound by VALU issue,
+//     and the table launch, which streams 2.4 KB per signature, issues VALU
+//     at about 85 % of the chain's rate too. A 1M
 //     chunk is four times the resident grid, so a workgroup slot that frees
 //     early takes the next workgroup. The earlier form, one kernel whose
 //     resident lanes each looped over four signatures, ran the same
 //     instruction count 4.6 % longer at a lower average occupancy, and so do
-//     these launches in chunks of one resident grid:
-//     keep the chunk well above the resident grid.
+//     these launches in chunks of one resident grid one after another (DESIGN
+//     4.2, round 10): keep the chunk well above the resident grid. A chunk
+//     may run in parts (hkv_layout.h HKV_REC_PART), two at a time on two
+//     streams, each in a slot of its own inside the chunk's scratch: the
+//     kernels take the slot's base as qs and the part as (i0, cn).
 // ---------------------------------------------------------------------------
 HKV_DEV uint4* zg_ptr(uint32_t* qs, uint32_t cn, uint32_t s) {
   return reinterpret_cast<uint4*>(qs) + (size_t)cn * QTAB_QUADS + (size_t)s * QTAB_ZG_QUADS;
@@ -1971,7 +1975,7 @@ HKV_DEV void gsum_lane(SoACView iv, const uint32_t* __restrict__ gtab, uint32_t 
 // (im, n_pad and a view built at each use: see the view's header)
 template <bool ILP, bool LATE>
 HKV_DEV void finish_lane(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad, const uint32_t* __restrict__ gtab,
-                         uint32_t* __restrict__ rare_ctr, uint32_t i, uint32_t flags,
+                         uint32_t* __restrict__ rare_ctr, uint32_t i0, uint32_t cn, uint32_t i, uint32_t flags,
                          const uint32_t* __restrict__ recs) {
   if constexpr (LATE) {
     if (i < n) flags = late_u1_lane(recs, i, SoAView{im, n_pad}, flags);
@@ -2080,9 +2084,10 @@ HKV_DEV void finish_lane(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad, 
     base = __shfl(base, lead);
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rmask >> 32),
                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)rmask, 0u));
-    // (at most n_pad rare lanes per batch; the clamp keeps a stale count from
-    // a failed earlier call inside the row)
-    if (rare && base + rank < n_pad) SoAView{im, n_pad}.put(IM_RARE_LIST, (size_t)base + rank, i);
+    // (the window's rare lanes are listed in its own [i0, i0 + cn) of the row,
+    // under its own counter: at most cn of them; the clamp keeps a stale count
+    // from a failed earlier call inside the window)
+    if (rare && base + rank < cn) SoAView{im, n_pad}.put(IM_RARE_LIST, (size_t)i0 + base + rank, i);
   }
   if (rare) {
     fo |= FLAG_RARE | (ainf ? FLAG_AINF : 0u);
@@ -2105,25 +2110,30 @@ HKV_DEV void finish_lane(uint32_t* __restrict__ im, uint32_t n, uint32_t n_pad, 
 
 template <bool ILP, bool LATE>
 __global__ void __launch_bounds__(WG, ILP ? 2 : HKV_FINISH_WAVES) hkv_finish_kernel(uint32_t* __restrict__ im, uint32_t n,
-                                                                                 uint32_t n_pad,
+                                                                                 uint32_t n_pad, uint32_t i0,
+                                                                                 uint32_t cn,
                                                                                  const uint32_t* __restrict__ gtab,
                                                                                  uint32_t* __restrict__ rare_ctr,
                                                                                  const uint32_t* __restrict__ recs) {
-  const uint32_t i = blockIdx.x * WG + threadIdx.x;
-  if (i >= n_pad) return;
-  finish_lane<ILP, LATE>(im, n, n_pad, gtab, rare_ctr, i, SoAView{im, n_pad}.get(IM_FLAGS, i), recs);
+  // the window [i0, i0 + cn) of the batch (whole waves: cn is a multiple of WG)
+  const uint32_t s = blockIdx.x * WG + threadIdx.x;
+  if (s >= cn) return;
+  const uint32_t i = i0 + s;
+  finish_lane<ILP, LATE>(im, n, n_pad, gtab, rare_ctr, i0, cn, i, SoAView{im, n_pad}.get(IM_FLAGS, i), recs);
 }
 
 // the exact slow path for the finish kernel's rare lanes: y0 = sqrt(w) of
 // the key's parity (no root: the key does not parse), B on E = (X, Y, Z y0)
 // (phi^-1 of B'), R = A + B with every degenerate case, the x compare.
-// Lane k takes the k-th compacted rare index; lanes past the count return.
-__global__ void __launch_bounds__(WG) hkv_rare_kernel(uint32_t* __restrict__ im, uint32_t n_pad,
-                                                      const uint32_t* __restrict__ rare_ctr) {
+// Lane k takes the k-th compacted rare index of the window [i0, i0 + cn)
+// (listed from i0 of the row, counted by the window's own word); lanes past
+// the count return.
+__global__ void __launch_bounds__(WG) hkv_rare_kernel(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i0,
+                                                      uint32_t cn, const uint32_t* __restrict__ rare_ctr) {
   const uint32_t k = blockIdx.x * WG + threadIdx.x;
-  if (k >= min(*rare_ctr, n_pad)) return;
+  if (k >= min(*rare_ctr, cn)) return;
   const SoAView iv = {im, n_pad};
-  const uint32_t i = iv.get(IM_RARE_LIST, k);
+  const uint32_t i = iv.get(IM_RARE_LIST, (size_t)i0 + k);
   const uint32_t flags = iv.get(IM_FLAGS, i);
   const bool rare = true;
   gej A, B;
@@ -2157,14 +2167,19 @@ __global__ void __launch_bounds__(WG) hkv_rare_kernel(uint32_t* __restrict__ im,
 }
 
 // verdicts: den^-1 by Montgomery's trick over VERDICT_BATCH signatures per lane
-// (signature i = t + k * stride; stride % WG == 0, so a wave's 64 lanes hold
-// 64 consecutive signatures and their verdicts leave as one ballot word)
-__global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t stride,
-                                                          uint32_t* __restrict__ bits, uint32_t n_words,
-                                                          uint32_t* __restrict__ rare_ctr) {
+// over the window [i0, i0 + cn) of the batch (signature i = i0 + t + k * stride;
+// i0, cn and stride are multiples of WG, so a wave's 64 lanes hold 64
+// consecutive signatures and their verdicts leave as one ballot word, and no
+// verdict word belongs to two windows)
+__global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__ im, uint32_t n_pad, uint32_t i0,
+                                                          uint32_t cn, uint32_t stride, uint32_t* __restrict__ bits,
+                                                          uint32_t n_words, uint32_t* __restrict__ rare_ctr) {
   // (im through ld8 / st8 and indexed here: see the view's header)
   const uint32_t t = blockIdx.x * WG + threadIdx.x;
-  if (t == 0) *rare_ctr = 0;  // re-arm for the next batch (the rare kernel has read it)
+  if (t == 0) *rare_ctr = 0;  // re-arm the window's count for the next batch (the rare kernel has read it)
+  // (the steps s = t + k * stride are window-relative, below VERDICT_BATCH * stride <= 2^32, and compared with
+  // cn before i0 is added: a window at the end of the largest batch does not wrap)
+  const uint32_t first = i0 + t;
   // one wave per SIMD at 1M: the loops are load-latency bound, so each
   // iteration's operands are loaded one iteration ahead
   fe c;
@@ -2172,17 +2187,18 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
   int kn = 0;
   {
     fe d;
-    SoACView::ld8(im, n_pad, IM_DEN.off, t, d.v);  // t < stride <= n_pad
-    uint32_t fl = im[(size_t)IM_FLAGS.off * n_pad + t];
+    SoACView::ld8(im, n_pad, IM_DEN.off, first, d.v);  // t < stride <= cn
+    uint32_t fl = im[(size_t)IM_FLAGS.off * n_pad + first];
 #pragma unroll 1
     for (int k = 0; k < VERDICT_BATCH; ++k) {
-      const uint32_t i = t + (uint32_t)k * stride;
-      if (i >= n_pad) break;
+      const uint32_t s = t + (uint32_t)k * stride;
+      if (s >= cn) break;
+      const uint32_t i = i0 + s;
       kn = k + 1;
       const uint32_t inext = i + stride;
       fe dn;
       uint32_t fn = 0;
-      if (k + 1 < VERDICT_BATCH && inext < n_pad) {
+      if (k + 1 < VERDICT_BATCH && s + stride < cn) {
         SoACView::ld8(im, n_pad, IM_DEN.off, inext, dn.v);
         fn = im[(size_t)IM_FLAGS.off * n_pad + inext];
       }
@@ -2202,7 +2218,7 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
     uint32_t r[8];
   };
   auto load_ops = [&](Ops& o, int k) {
-    const uint32_t i = t + (uint32_t)k * stride;
+    const uint32_t i = first + (uint32_t)k * stride;
     o.f = im[(size_t)IM_FLAGS.off * n_pad + i];
     if (k > 0) SoACView::ld8(im, n_pad, IM_C.off, i - stride, o.prev.v);
     SoACView::ld8(im, n_pad, IM_DEN.off, i, o.d.v);
@@ -2214,7 +2230,7 @@ __global__ void __launch_bounds__(WG) hkv_yverdict_kernel(uint32_t* __restrict__
   if (kn > 0) load_ops(cur, kn - 1);
 #pragma unroll 1
   for (int k = kn - 1; k >= 0; --k) {
-    const uint32_t i = t + (uint32_t)k * stride;  // < n_pad; kn is wave-uniform (n_pad, stride multiples of 64)
+    const uint32_t i = first + (uint32_t)k * stride;  // < i0 + cn; kn is wave-uniform (cn, stride multiples of 64)
     Ops nxt;
     if (k > 0) load_ops(nxt, k - 1);
     const uint32_t f = cur.f;
@@ -3029,22 +3045,19 @@ hipError_t launch_prologue(const RecPlan& p, const RecOps& r, hipStream_t st) {
   hipLaunchKernelGGL(hkv_glv_kernel, dim3(ceil_div(p.n_pad, WG)), dim3(WG), 0, st, p.n_pad, r.im);
   return hipGetLastError();
 }
-// TableChain (2a): the table and chain launches over the plan's chunks (each
-// a multiple of WG; qs holds a chunk's tables and Zg slots)
-static hipError_t launch_table_chain(const RecPlan& p, const RecOps& r, hipStream_t st) {
-  if (p.chunk_len < (uint32_t)WG || p.chunk_len % WG != 0) return hipErrorInvalidValue;
-  for (uint32_t k = 0; k < p.n_chunks; ++k) {
-    const uint32_t i0 = p.chunk(k).i0, cn = p.chunk(k).cn;
-    hipLaunchKernelGGL(hkv_qtable_kernel, dim3(cn / WG), dim3(WG), 0, st, (const uint32_t*)r.im, r.n, p.n_pad, i0, cn,
-                       r.qs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(hkv_chain_kernel, dim3(cn / WG), dim3(WG), 0, st, r.im, r.n, p.n_pad, i0, cn,
-                       (const uint32_t*)r.qs, i0 == 0 ? r.clk : nullptr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// TableChain (2a): the table and chain launches of part k of the plan (a
+// multiple of WG signatures), its tables and Zg slots in the part's slot of qs
+hipError_t launch_table_chain(const RecPlan& p, const RecOps& r, uint32_t k, hipStream_t st) {
+  if (p.shape != Shape::TableChain || k >= p.n_parts) return hipErrorInvalidValue;
+  const uint32_t i0 = p.part(k).i0, cn = p.part(k).cn, slot = p.qs_slots == 2 ? RecPlan::part_slot(k) : 0u;
+  if (cn < (uint32_t)WG || cn % WG != 0) return hipErrorInvalidValue;
+  uint32_t* qs = r.qs + p.slot_quads(slot) * 4;
+  hipLaunchKernelGGL(hkv_qtable_kernel, dim3(cn / WG), dim3(WG), 0, st, (const uint32_t*)r.im, r.n, p.n_pad, i0, cn, qs);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hkv_chain_kernel, dim3(cn / WG), dim3(WG), 0, st, r.im, r.n, p.n_pad, i0, cn, (const uint32_t*)qs,
+                     i0 == 0 ? r.clk : nullptr);
+  return hipGetLastError();
 }
 static StdArgs std_args(const StdOps& o) {
   return StdArgs{o.txs, o.n_tx, o.txt, o.scripts, o.scripts_len, o.jobs, o.forkid, nullptr, nullptr, nullptr, nullptr};
@@ -3070,8 +3083,7 @@ hipError_t launch_ecmult(const RecPlan& p, const RecOps& r, const StdOps* std_pr
       hipLaunchKernelGGL((hkv_ecmult_kernel<true, false>), dim3(p.grid), dim3(WG), 0, st, r.im, r.n, p.n_pad, r.qs,
                          r.clk, StdArgs{});
       break;
-    case Shape::TableChain: return launch_table_chain(p, r, st);
-    default: return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;  // (TableChain: launch_table_chain, part by part)
   }
   return hipGetLastError();
 }
@@ -3117,27 +3129,30 @@ static hipError_t launch_mid_std(const RecPlan& p, const RecOps& r, const StdOps
                      std_args(o));
   return hipGetLastError();
 }
-hipError_t launch_finish(const RecPlan& p, const RecOps& r, uint32_t* rare_ctr, const void* late_recs,
+hipError_t launch_finish(const RecPlan& p, const RecOps& r, RecChunk w, uint32_t* rare_ctr, const void* late_recs,
                          hipStream_t st) {
   if (p.shape != Shape::Mid && p.shape != Shape::TableChain) return hipErrorInvalidValue;
+  const uint32_t i0 = w.i0, cn = w.cn;
+  if (cn < (uint32_t)WG || cn % WG != 0 || i0 % WG != 0 || (uint64_t)i0 + cn > p.n_pad) return hipErrorInvalidValue;
   const bool paired = p.shape == Shape::Mid;  // (the paired-product instance)
   const uint32_t* lr = static_cast<const uint32_t*>(late_recs);
-  const dim3 g(p.n_pad / WG), b(WG);
+  const dim3 g(cn / WG), b(WG);
   if (paired && lr)
-    hipLaunchKernelGGL((hkv_finish_kernel<true, true>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
+    hipLaunchKernelGGL((hkv_finish_kernel<true, true>), g, b, 0, st, r.im, r.n, p.n_pad, i0, cn, r.gtab, rare_ctr, lr);
   else if (paired)
-    hipLaunchKernelGGL((hkv_finish_kernel<true, false>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
+    hipLaunchKernelGGL((hkv_finish_kernel<true, false>), g, b, 0, st, r.im, r.n, p.n_pad, i0, cn, r.gtab, rare_ctr, lr);
   else if (lr)
-    hipLaunchKernelGGL((hkv_finish_kernel<false, true>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
+    hipLaunchKernelGGL((hkv_finish_kernel<false, true>), g, b, 0, st, r.im, r.n, p.n_pad, i0, cn, r.gtab, rare_ctr, lr);
   else
-    hipLaunchKernelGGL((hkv_finish_kernel<false, false>), g, b, 0, st, r.im, r.n, p.n_pad, r.gtab, rare_ctr, lr);
+    hipLaunchKernelGGL((hkv_finish_kernel<false, false>), g, b, 0, st, r.im, r.n, p.n_pad, i0, cn, r.gtab, rare_ctr, lr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(hkv_rare_kernel, dim3(p.n_pad / WG), dim3(WG), 0, st, r.im, p.n_pad, (const uint32_t*)rare_ctr);
+  hipLaunchKernelGGL(hkv_rare_kernel, g, b, 0, st, r.im, p.n_pad, i0, cn, (const uint32_t*)rare_ctr);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(hkv_yverdict_kernel, dim3(p.verdict_stride / WG), dim3(WG), 0, st, r.im, p.n_pad,
-                     p.verdict_stride, r.bits, r.n_words, rare_ctr);
+  const uint32_t stride = verdict_stride_of(cn);  // (the whole batch as one window: p.verdict_stride)
+  hipLaunchKernelGGL(hkv_yverdict_kernel, dim3(stride / WG), b, 0, st, r.im, p.n_pad, i0, cn, stride, r.bits,
+                     r.n_words, rare_ctr);
   return hipGetLastError();
 }
 hipError_t launch_gen_pool(uint64_t seed, uint32_t npool, uint32_t* pool, hipStream_t st) {

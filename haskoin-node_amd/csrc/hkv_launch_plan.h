@@ -24,7 +24,19 @@ struct Geometry {
   // standard inputs per chunk of a batch past one resident grid (default
   // 2^20; env HKV_STD_CHUNK at open, for tests: a multiple of 64)
   size_t std_chunk = 0;
+  // signatures per part of a table / chain batch that runs as a two-stream
+  // pipeline (RecPlan::part_len; default HKV_REC_PART; env HKV_REC_PART at
+  // open, for tests: rounded up to PART_ALIGN). 0: no parts, every chunk runs
+  // whole on the caller's stream
+  size_t rec_part = 0;
 };
+
+// Part boundaries are whole workgroups and whole groups of VERDICT_BATCH
+// verdict words, so no verdict word and no batched-inversion group of a
+// windowed launch straddles two parts.
+constexpr size_t PART_ALIGN = (size_t)VERDICT_BATCH * 32 % WG == 0 ? (size_t)VERDICT_BATCH * 32
+                                                                   : (size_t)VERDICT_BATCH * 32 * WG;
+static_assert(PART_ALIGN % WG == 0 && PART_ALIGN % ((size_t)VERDICT_BATCH * 32) == 0, "part alignment");
 
 // A batch of at most 1 / SPLIT_DIV of the resident grid (half a wave per SIMD)
 // runs a small-batch kernel: a shorter dependency chain where latency, not
@@ -75,6 +87,29 @@ struct RecPlan {
     const uint64_t left = n_pad - i0;
     return RecChunk{(uint32_t)i0, (uint32_t)(left < chunk_len ? left : chunk_len)};
   }
+  // TableChain: part(0 .. n_parts) cover [0, n_pad) in order, each through
+  // table, chain, finish, rare and verdict launches of its own window. With
+  // qs_slots == 2 the parts cut the batch, not a chunk, every part_len
+  // signatures (a multiple of PART_ALIGN), and part k runs on stream
+  // part_stream(k) with its tables and Zg slots in slot part_slot(k) of qs,
+  // part_len * (QTAB_QUADS + QTAB_ZG_QUADS) quads each, beside part k + 1 in
+  // the other. With one slot the parts are the chunks, one after another on
+  // the caller's stream, and the finish launches take the whole batch as one
+  // window. Other shapes: one part, the batch.
+  uint32_t part_len, n_parts, qs_slots;
+  RecChunk part(uint32_t k) const {
+    const uint64_t i0 = (uint64_t)k * part_len;
+    const uint64_t left = n_pad - i0;
+    return RecChunk{(uint32_t)i0, (uint32_t)(left < part_len ? left : part_len)};
+  }
+  // the stream (0 the caller's, 1 the pipe stream) and the qs slot of part k
+  // of a two-slot plan. Both alternate, so the part that overwrites a slot
+  // follows the slot's last chain launch in its own stream's order: the
+  // pipeline (hkv_api.cpp enqueue_table_chain) checks that per part, and
+  // tests/pipe_plan.cpp models it
+  static constexpr uint32_t part_stream(uint32_t k) { return k & 1u; }
+  static constexpr uint32_t part_slot(uint32_t k) { return k & 1u; }
+  size_t slot_quads(uint32_t slot) const { return (size_t)slot * part_len * (QTAB_QUADS + QTAB_ZG_QUADS); }
 };
 
 namespace plan_detail {
@@ -86,6 +121,15 @@ inline Shape shape_of(const Geometry& g, size_t n_pad) {
   return n_pad <= (size_t)BLK_SIGS * g.n_cu ? Shape::Block : Shape::Pair;
 }
 }  // namespace plan_detail
+
+// The verdict kernel's lanes for a window of cn signatures (a multiple of WG):
+// VERDICT_BATCH per lane, whole workgroups, at least MIN_INV_LANES (or one per
+// signature). At most cn, so every lane's first signature lies in the window.
+inline uint32_t verdict_stride_of(size_t cn) {
+  const size_t min_lanes = cn < MIN_INV_LANES ? cn : MIN_INV_LANES;
+  const size_t ver = plan_detail::round_up((cn + VERDICT_BATCH - 1) / VERDICT_BATCH, WG);
+  return (uint32_t)(ver < min_lanes ? min_lanes : ver);
+}
 
 // A batch of n records (1 <= n <= 0xFFFFFF00) at once on this device.
 inline RecPlan plan_records(const Geometry& g, size_t n) {
@@ -107,8 +151,7 @@ inline RecPlan plan_records(const Geometry& g, size_t n) {
   const size_t min_lanes = n_pad < MIN_INV_LANES ? n_pad : MIN_INV_LANES;
   const size_t inv = (n_pad + BATCH_INV - 1) / BATCH_INV;
   p.inv_stride = (uint32_t)(inv > MIN_INV_LANES ? inv : min_lanes);
-  const size_t ver = round_up((n_pad + VERDICT_BATCH - 1) / VERDICT_BATCH, WG);
-  p.verdict_stride = (uint32_t)(ver < min_lanes ? min_lanes : ver);
+  p.verdict_stride = verdict_stride_of(n_pad);
   p.qs_quads = grid_lanes(g) * QTAB_QUADS;
   p.chunk_len = p.n_pad;
   p.n_chunks = 1;
@@ -118,6 +161,19 @@ inline RecPlan plan_records(const Geometry& g, size_t n) {
     if (quads > p.qs_quads) p.qs_quads = quads;
     p.chunk_len = (uint32_t)chunk;
     p.n_chunks = (uint32_t)((n_pad + chunk - 1) / chunk);
+  }
+  p.part_len = p.chunk_len;
+  p.n_parts = p.n_chunks;
+  p.qs_slots = 1;
+  if (p.shape == Shape::TableChain && g.rec_part != 0) {
+    // two parts in flight: more than one part, none longer than a chunk, and
+    // both slots inside the scratch the plan reserves anyway
+    const size_t part = round_up(g.rec_part, PART_ALIGN);
+    if (part < n_pad && part <= p.chunk_len && 2 * part * (QTAB_QUADS + QTAB_ZG_QUADS) <= p.qs_quads) {
+      p.part_len = (uint32_t)part;
+      p.n_parts = (uint32_t)((n_pad + part - 1) / part);
+      p.qs_slots = 2;
+    }
   }
   return p;
 }

@@ -196,6 +196,16 @@ constexpr int QTAB_QUADS = QTAB_ENTRIES * QTAB_QUADS_PER_ENTRY;
 #ifndef HKV_REC_CHUNK
 #define HKV_REC_CHUNK (1u << 20)
 #endif
+// A chunk runs in parts of this many signatures, two at a time on two streams
+// (hkv_launch_plan.h RecPlan::part_len): each part's tables and Zg slots take
+// one of two slots inside the chunk's scratch, laid out as above with cn the
+// part's length. 0: chunks run whole. Two resident grids of an MI355X per
+// part, so a 2^20 chunk in two parts, measured best on the 1M batch among
+// half a grid, one and two (120.8 / 122.1, 128.5 /
+// 128.0 and 129.6 / 128.7 M verifies/s against 125.5 / 125.3 whole).
+#ifndef HKV_REC_PART
+#define HKV_REC_PART (1u << 19)
+#endif
 constexpr int QTAB_ZG_QUADS = 2;
 
 constexpr int WG = 256;                // threads per workgroup (4 waves)

@@ -82,6 +82,7 @@ EXPORTS = {
     "hkv_debug_ms_scratch": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
     "hkv_debug_q_scratch": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "hkv_debug_launch_shape": (c_int, [c_void_p, c_int, c_uint32, c_size_t, POINTER(c_uint32)]),
+    "hkv_debug_rec_parts": (c_int, [c_void_p, c_int, c_size_t, POINTER(c_uint32), POINTER(c_uint32)]),
     "hkv_debug_ms_tail_counts": (c_int, [c_void_p, c_int, POINTER(c_uint64)]),
     "hkv_batch_alloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "hkv_batch_free": (None, [c_void_p]),
@@ -165,7 +166,7 @@ EXPORTS = {
 
 # measurement hooks a library variant built before them may lack; every other
 # export is required (tests/test_abi.py checks the in-tree build has them all)
-MEASUREMENT_ONLY = {"hkv_profile_group_stamps", "hkv_debug_q_scratch", "hkv_debug_launch_shape"}
+MEASUREMENT_ONLY = {"hkv_profile_group_stamps", "hkv_debug_q_scratch", "hkv_debug_launch_shape", "hkv_debug_rec_parts"}
 
 _LIB = None
 

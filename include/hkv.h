@@ -176,6 +176,14 @@ int hkv_debug_q_scratch(hkv_ctx* ctx, int dev, size_t* bytes, size_t* chunk);
  * out[2] = the first chunk's length (records: padded to 256; the chunk of the
  * table and chain launches); out[3] = the number of chunks. */
 int hkv_debug_launch_shape(hkv_ctx* ctx, int dev, uint32_t kind, size_t n, uint32_t out[4]);
+/* Read-only test hook: the parts a batch of n records would run in on device
+ * dev, from the same plan; nothing is launched. A batch of shape 4 whose plan
+ * holds two parts at a time (the env hook HKV_REC_PART at open sets their
+ * length) runs its table, chain, finish and verdict launches part by part on
+ * two streams: *part_len = the parts' length (the last may be shorter),
+ * *n_parts > 1 their number. Otherwise the parts are the chunks of
+ * hkv_debug_launch_shape, or the batch. */
+int hkv_debug_rec_parts(hkv_ctx* ctx, int dev, size_t n, uint32_t* part_len, uint32_t* n_parts);
 /* Read-only test hook: what device dev's last multisig tail launch saw and
  * did, read after every call enqueued so far has completed. out[0] = the
  * scan's total it ran on (candidate records | key-check records << 32),
