@@ -42,6 +42,8 @@ HKV_DEV void gej_cmov(gej& r, const gej& a, bool f) {
   fe_cmov(r.z, a.z, f);
 }
 
+// FC (here and in gej_add_tail, gej_add_ge_core, gej_accumulate): the products
+// run the scans' fast forms (hkv_field.h); the throughput launches ask for it.
 // r = 2a for a = 0 (3M + 4S), returned as the same point scaled by 1/2:
 // with A = X^2, B = Y^2, C = B^2, M = X*B, E' = 3A/2,
 //   X3' = E'^2 - 2M, Y3' = E'(M - X3') - C, Z3' = Y*Z,
@@ -52,19 +54,20 @@ HKV_DEV void gej_cmov(gej& r, const gej& a, bool f) {
 // infinity; y != 0 on secp256k1. r may alias a.
 // -Y3' = B^2 + E'(X3' - M) is one sum scan (C is never formed), negated by
 // complement.
+template <bool FC = false>
 HKV_DEV void gej_double(gej& r, const gej& a) {
   fe A, B, M, E, t, u;
-  fe_sqr(A, a.x);
-  fe_sqr(B, a.y);
-  fe_mul(M, a.x, B);
+  fe_sqr<FC>(A, a.x);
+  fe_sqr<FC>(B, a.y);
+  fe_mul<FC>(M, a.x, B);
   fe_mul_small(E, A, 3);
   fe_half(E, E);            // E' = 3A/2
-  fe_mul(r.z, a.y, a.z);    // Z3' = YZ
-  fe_sqr(t, E);
+  fe_mul<FC>(r.z, a.y, a.z);    // Z3' = YZ
+  fe_sqr<FC>(t, E);
   fe_shl(u, M, 1);
   fe_sub(r.x, t, u);        // X3' = E'^2 - 2M
   fe_sub(t, r.x, M);
-  fe_sqrmul_sum(t, B, E, t);  // -Y3' = B^2 + E'(X3' - M)
+  fe_sqrmul_sum<FC>(t, B, E, t);  // -Y3' = B^2 + E'(X3' - M)
   fe_neg_compl(r.y, t);
 }
 
@@ -73,18 +76,19 @@ HKV_DEV void gej_double(gej& r, const gej& a) {
 // Z3 = Z1 H, and -Y3 = R(X3 - V) + Y1 H^3 as one sum scan, negated by
 // complement. H != 0. r may alias a: a.x is last read before r.x is written,
 // and a.y is read after r.z and r.x are written, never after r.y.
+template <bool FC = false>
 HKV_DEV void gej_add_tail(gej& r, const gej& a, const fe& h, const fe& rr) {
   fe hh, hhh, v, t, t2;
-  fe_sqr(hh, h);
-  fe_mul(hhh, h, hh);       // H^3
-  fe_mul(v, a.x, hh);       // V = X1 H^2
-  fe_mul(r.z, a.z, h);      // Z3 = Z1 H
-  fe_sqr(t, rr);
+  fe_sqr<FC>(hh, h);
+  fe_mul<FC>(hhh, h, hh);       // H^3
+  fe_mul<FC>(v, a.x, hh);       // V = X1 H^2
+  fe_mul<FC>(r.z, a.z, h);      // Z3 = Z1 H
+  fe_sqr<FC>(t, rr);
   fe_sub(t, t, hhh);
   fe_shl(t2, v, 1);
   fe_sub(r.x, t, t2);       // X3 = R^2 - H^3 - 2V
   fe_sub(v, r.x, v);
-  fe_mul_sum(v, rr, v, a.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
+  fe_mul_sum<FC>(v, rr, v, a.y, hhh);  // -Y3 = R(X3 - V) + Y1 H^3
   fe_neg_compl(r.y, v);
 }
 
@@ -94,18 +98,19 @@ HKV_DEV void gej_add_tail(gej& r, const gej& a, const fe& h, const fe& rr) {
 // lives on the isomorphic curve of scale Zg). 8M + 3S.
 // Outputs hz = (H == 0), rz = (R == 0); when hz the result is garbage and the
 // caller must substitute 2a (rz) or infinity (!rz). Writes the z-ratio H.
+template <bool FC = false>
 HKV_DEV void gej_add_ge_core(gej& r, const gej& a, const fe& az, const fe& bx, const fe& by,
                              bool& hz, bool& rz, fe* zr) {
   fe z2, u2, s2, h, rr, t;
-  fe_sqr(z2, az);
-  fe_mul(u2, bx, z2);
-  fe_mul(t, az, z2);
-  fe_mul(s2, by, t);
+  fe_sqr<FC>(z2, az);
+  fe_mul<FC>(u2, bx, z2);
+  fe_mul<FC>(t, az, z2);
+  fe_mul<FC>(s2, by, t);
   fe_sub(h, u2, a.x);
   fe_sub(rr, s2, a.y);
   hz = fe_is_zero(h);
   rz = fe_is_zero(rr);
-  gej_add_tail(r, a, h, rr);
+  gej_add_tail<FC>(r, a, h, rr);
   if (zr) *zr = h;
 }
 
@@ -119,24 +124,25 @@ HKV_DEV void gej_add_ge_core(gej& r, const gej& a, const fe& az, const fe& bx, c
 // computed in place under the lane mask live && H != 0: lanes that do not
 // add keep their point without a copy, and acc = +-T (H == 0, rare) is then
 // resolved exactly by a masked doubling or by going to infinity.
+template <bool FC = false>
 HKV_DEV void gej_accumulate(gej& acc, bool& inf, const fe& az, const fe& tx, const fe& ty, bool take) {
   fe h, rr;
   {
     fe z2, t;
-    fe_sqr(z2, az);
-    fe_mul(h, tx, z2);        // U2
-    fe_mul(t, az, z2);
-    fe_mul(rr, ty, t);        // S2
+    fe_sqr<FC>(z2, az);
+    fe_mul<FC>(h, tx, z2);        // U2
+    fe_mul<FC>(t, az, z2);
+    fe_mul<FC>(rr, ty, t);        // S2
   }
   fe_sub(h, h, acc.x);        // H = U2 - X1
   fe_sub(rr, rr, acc.y);      // R = S2 - Y1
   const bool live = take && !inf;
   const bool hz = fe_is_zero(h);
-  if (live && !hz) gej_add_tail(acc, acc, h, rr);
+  if (live && !hz) gej_add_tail<FC>(acc, acc, h, rr);
   const bool degen = live && hz;
   if (__builtin_expect(__any(degen), 0)) {
     const bool rz = fe_is_zero(rr);
-    if (degen && rz) gej_double(acc, acc);   // T == acc
+    if (degen && rz) gej_double<FC>(acc, acc);   // T == acc
     inf = inf || (degen && !rz);             // T == -acc
   }
 }

@@ -67,6 +67,23 @@ enum {
   HKV_DBG_FE_SQRMUL_SUM_RA = 43,  // op 39, r aliases a
   HKV_DBG_FE_SQRMUL_SUM_RD = 44,  // op 39, r aliases d
   HKV_DBG_FE_MUL_SUM_RB = 45,  // op 38, r aliases b (the form gej_accumulate and gej_add_ge_core use)
+  // Ops 1, 2, 22, 38, 39, 41..45 and the group ops 64, 66 run the FC = true forms of
+  // their wrapper or formula (hkv_field.h: the fast scan, the exact scan on a
+  // non-zero rare mask), the forms the chain and finish launches run; the
+  // results are bit for bit those of the FC = false forms, which every other
+  // caller runs. These ops no longer reach the FC = false forms directly;
+  // fe_inv / fe_sqrt (ops 5, 6), ecmult_simple (ops 10, 71) and gej_add_var
+  // (op 68) run them.
+  // The scans' fast forms alone (hkv_mul_asm.h *_fc, whatever HKV_FIRST_CARRY
+  // selects for the wrappers), operands as in the wrapper op named: out[0..8)
+  // = r, out[8..10) = T, out[10] = the lane's bit of the rare mask (r and T
+  // mean nothing where it is 1).
+  HKV_DBG_FC_MUL = 46,          // as op 1
+  HKV_DBG_FC_SQR = 47,          // as op 2
+  HKV_DBG_FC_MUL_ADD = 48,      // as op 22
+  HKV_DBG_FC_MUL_SUM = 49,      // as op 38
+  HKV_DBG_FC_SQRMUL_SUM = 50,   // as op 39
+  HKV_DBG_FC_MUL_MASK = 51,     // op 46's whole rare mask of the lane's wave in out[0..2) (every active lane writes it)
   // Group ops (hkv_debug_group_kernel): lane i takes rows 2i and 2i + 1 (n
   // even, n / 2 lanes). a: k1 | z1, b: k2 | w. The lane's points are
   // P1 = k1 G and P2 = k2 G (ecmult_simple; a zero scalar is infinity), P1

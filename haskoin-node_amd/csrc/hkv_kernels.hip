@@ -549,12 +549,12 @@ HKV_DEV void qtab_load(const uint32_t* __restrict__ qs, uint32_t n_lanes, uint32
 template <bool ILP>
 HKV_DEV void ec_double(gej& acc) {
   if constexpr (ILP) gej_double_ilp(acc, acc);
-  else gej_double(acc, acc);
+  else gej_double<true>(acc, acc);  // 3 or 4 waves per SIMD: the fast scans (hkv_field.h FC)
 }
 template <bool ILP>
 HKV_DEV void ec_accumulate(gej& acc, bool& inf, const fe& az, const fe& tx, const fe& ty, bool take) {
   if constexpr (ILP) gej_accumulate_ilp(acc, inf, az, tx, ty, take);
-  else gej_accumulate(acc, inf, az, tx, ty, take);
+  else gej_accumulate<true>(acc, inf, az, tx, ty, take);
 }
 
 template <bool ILP = false>
@@ -2606,8 +2606,8 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
     for (int k = 0; k < 8; ++k) { res[k] = r1.v[k]; res[8 + k] = r2.v[k]; }
   };
   switch (op) {
-    case HKV_DBG_FE_MUL: fe_mul(z, x, y); norm_raw(z); break;
-    case HKV_DBG_FE_SQR: fe_sqr(z, x); norm_raw(z); break;
+    case HKV_DBG_FE_MUL: fe_mul<true>(z, x, y); norm_raw(z); break;
+    case HKV_DBG_FE_SQR: fe_sqr<true>(z, x); norm_raw(z); break;
     case HKV_DBG_FE_ADD: fe_add(z, x, y); norm_raw(z); break;
     case HKV_DBG_FE_SUB: fe_sub(z, x, y); norm_raw(z); break;
     case HKV_DBG_FE_INV: fe_inv(z, x); fe_normalize(z); for (int k = 0; k < 8; ++k) res[k] = z.v[k]; break;
@@ -2663,7 +2663,7 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
     case HKV_DBG_FE_MUL_ADD: {
       fe xn;
       load_next(xn, a);
-      fe_mul_add(z, x, y, xn);
+      fe_mul_add<true>(z, x, y, xn);
       raw_norm(z);
       break;
     }
@@ -2707,10 +2707,10 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
       fe xn, yn;
       load_next(xn, a);
       load_next(yn, b);
-      if (op == HKV_DBG_FE_MUL_SUM_RA) { fe_mul_sum(x, x, y, xn, yn); z = x; }
-      else if (op == HKV_DBG_FE_MUL_SUM_RB) { fe_mul_sum(y, x, y, xn, yn); z = y; }
-      else if (op == HKV_DBG_FE_MUL_SUM_RD) { fe_mul_sum(yn, x, y, xn, yn); z = yn; }
-      else fe_mul_sum(z, x, y, xn, yn);
+      if (op == HKV_DBG_FE_MUL_SUM_RA) { fe_mul_sum<true>(x, x, y, xn, yn); z = x; }
+      else if (op == HKV_DBG_FE_MUL_SUM_RB) { fe_mul_sum<true>(y, x, y, xn, yn); z = y; }
+      else if (op == HKV_DBG_FE_MUL_SUM_RD) { fe_mul_sum<true>(yn, x, y, xn, yn); z = yn; }
+      else fe_mul_sum<true>(z, x, y, xn, yn);
       raw_norm(z);
       break;
     }
@@ -2719,13 +2719,39 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
     case HKV_DBG_FE_SQRMUL_SUM_RD: {
       fe xn;
       load_next(xn, a);
-      if (op == HKV_DBG_FE_SQRMUL_SUM_RA) { fe_sqrmul_sum(x, x, y, xn); z = x; }
-      else if (op == HKV_DBG_FE_SQRMUL_SUM_RD) { fe_sqrmul_sum(xn, x, y, xn); z = xn; }
-      else fe_sqrmul_sum(z, x, y, xn);
+      if (op == HKV_DBG_FE_SQRMUL_SUM_RA) { fe_sqrmul_sum<true>(x, x, y, xn); z = x; }
+      else if (op == HKV_DBG_FE_SQRMUL_SUM_RD) { fe_sqrmul_sum<true>(xn, x, y, xn); z = xn; }
+      else fe_sqrmul_sum<true>(z, x, y, xn);
       raw_norm(z);
       break;
     }
     case HKV_DBG_FE_NEG_COMPL: fe_neg_compl(z, x); raw_norm(z); break;
+    case HKV_DBG_FC_MUL:
+    case HKV_DBG_FC_SQR:
+    case HKV_DBG_FC_MUL_ADD:
+    case HKV_DBG_FC_MUL_SUM:
+    case HKV_DBG_FC_SQRMUL_SUM:
+    case HKV_DBG_FC_MUL_MASK: {
+      fe xn, yn;
+      load_next(xn, a);
+      load_next(yn, b);
+      uint64_t T = 0, rare;
+      if (op == HKV_DBG_FC_SQR) rare = sqr256_red_ps_fc(z.v, T, x.v, x.v);
+      else if (op == HKV_DBG_FC_MUL_ADD) rare = mul256_red_add_ps_fc(z.v, T, x.v, y.v, xn.v);
+      else if (op == HKV_DBG_FC_MUL_SUM) rare = mul256_red_sum_ps_fc(z.v, T, x.v, y.v, xn.v, yn.v);
+      else if (op == HKV_DBG_FC_SQRMUL_SUM) rare = sqrmul256_red_sum_ps_fc(z.v, T, x.v, y.v, xn.v);
+      else rare = mul256_red_ps_fc(z.v, T, x.v, y.v);
+      if (op == HKV_DBG_FC_MUL_MASK) {
+        res[0] = (uint32_t)rare;
+        res[1] = (uint32_t)(rare >> 32);
+        break;
+      }
+      for (int k = 0; k < 8; ++k) res[k] = z.v[k];
+      res[8] = (uint32_t)T;
+      res[9] = (uint32_t)(T >> 32);
+      res[10] = (uint32_t)(rare >> (threadIdx.x & 63u)) & 1u;
+      break;
+    }
     default: break;
   }
 #pragma unroll
@@ -2793,9 +2819,9 @@ __global__ void __launch_bounds__(WG) hkv_debug_group_kernel(uint32_t op, uint32
     acc.z = z1;
     bool inf = !ok1 || (sel & 2u) != 0;
     switch (op) {
-      case HKV_DBG_GEJ_DOUBLE: gej_double(acc, acc); break;
+      case HKV_DBG_GEJ_DOUBLE: gej_double<true>(acc, acc); break;
       case HKV_DBG_GEJ_DOUBLE_ILP: gej_double_ilp(acc, acc); break;
-      case HKV_DBG_GEJ_ACCUMULATE: gej_accumulate(acc, inf, acc.z, p2.x, p2.y, take); break;
+      case HKV_DBG_GEJ_ACCUMULATE: gej_accumulate<true>(acc, inf, acc.z, p2.x, p2.y, take); break;
       case HKV_DBG_GEJ_ACCUMULATE_ILP: gej_accumulate_ilp(acc, inf, acc.z, p2.x, p2.y, take); break;
       case HKV_DBG_GEJ_ADD_AFFINE_COMPLETE: gej_add_affine_complete(acc, inf, p2, take); break;
       case HKV_DBG_GEJ_ADD_VAR: {

@@ -7,6 +7,16 @@ into the column's top word. The carry is consumed >= 2 instructions after it
 is written (gfx950 VALU-writes-SGPR -> VALU-reads-SGPR spacing); three SGPR
 pairs rotate. Between columns the accumulator shifts by 32 bits (C level).
 
+The single reduced scans also get a fast form (*_fc): a column's accumulator
+starts below 2^43 + 2^32, so its first full product can carry only if both
+limbs lie within about 2^11 of 2^32. That product's carry-out is kept in an
+SGPR pair of its own and not added; products that provably cannot carry take
+no v_addc at all; after the last column the kept pairs are OR-ed into the
+rare mask the form returns (ColumnBounds, fast_block, rare_or). The bounds
+are computed by interval arithmetic over all-ones operands and asserted for
+every column of every scan whenever the header is rendered.
+    python tools/gen_mul_asm.py --schedule   (the fast forms' product order, JSON)
+
     python tools/gen_mul_asm.py
 """
 import os
@@ -126,7 +136,157 @@ def scan_block(pairs, mode):
             f'      : {ins});')
 
 
-def reduced_scan(name, cols, doc, addend=False):
+# ---------------------------------------------------------------------------
+# fast forms: no carry add for a column's first product
+# ---------------------------------------------------------------------------
+W32 = 2**32 - 1
+SEED_BOUND = 2**43            # a column's accumulator after its seeding mads
+CHECK_BOUND = 2**43 + 2**32   # ... and after the products against the 1-bit limb
+
+
+def op_max(nm):
+    """Largest value of a limb operand: d[8] = a[7] >> 31 is one bit."""
+    return 1 if nm.endswith("[8]") and nm[0] == "d" else W32
+
+
+class ColumnBounds:
+    """Interval arithmetic over all-ones operands for one stream of a fast
+    scan: v is the largest true value (carries included) of the running
+    column, so the next column's accumulator is at most v >> 32.
+
+    classify() orders a column (products with an operand below 2^32 first) and
+    gives every product its class:
+      "free"   acc_max + product_max < 2^64: the mad cannot carry, no v_addc;
+      "check"  the first other product, met with acc < 2^43 + 2^32: it carries
+               only if the product is >= 2^64 - acc, so its carry-out goes to
+               the scan's rare mask and not to top;
+      "add"    every later product: one v_addc into top, as in the exact form.
+    Both bounds are asserted here for every column of every scan kind."""
+
+    def __init__(self):
+        self.v = 0
+        self.log = []
+
+    def high_start(self):
+        self.v >>= 32
+
+    def low_start(self, first, addend):
+        carry_in = 0 if first else (self.v >> 32) + W32   # prevhi + init, init = (top << 32) | h[j-1]
+        self.v = carry_in + W32 * 977 + (W32 if addend else 0)
+        assert self.v < SEED_BOUND, self.v
+
+    def classify(self, pairs):
+        order = sorted(pairs, key=lambda pr: min(op_max(pr[0]), op_max(pr[1])) == W32)
+        classes, state = [], "free"
+        for x, y in order:
+            pm = op_max(x) * op_max(y)
+            if state == "free" and self.v + pm < 2**64:
+                cls = "free"
+            elif state == "free" and self.v < CHECK_BOUND:
+                cls, state = "check", "add"
+            else:
+                cls, state = "add", "add"
+            self.log.append((cls, self.v, pm))
+            self.v += pm
+            classes.append(cls)
+        return order, classes
+
+
+def fast_block(pairs, classes, mode, addend, kept):
+    """asm for one column of a fast scan: scan_block (three rotating carry
+    pairs, a carry read two mads after its own) with the products classed by
+    ColumnBounds.classify. A free product's carry pair has no reader. The
+    check product writes its carry-out to a pair of its own, rk<kept>, which
+    stays live to the end of the scan (rare_or): a scalar OR right behind the
+    mad makes the scalar unit wait for the vector pipeline in every column
+    (measured: profiles/r14_first_carry/README.md section 1).
+    -> (text, the column has no v_addc: top = 0 at the C level, pairs kept so far)"""
+    has_add, has_check = "add" in classes, "check" in classes
+    outs = [("acc", '"+v"' if mode == "acc" else '"=&v"', "acc" if mode == "acc" else "accn")]
+    if has_add:
+        outs.append(("top", '"=&v"', "top"))
+    outs += [(f"c{i}", '"=&s"', f"c{i}") for i in range(3)]
+    if has_check:
+        outs.append(("rk", '"=&s"', f"rk{kept}"))
+    ins = []
+    if mode == "red0":
+        ins += [("h0", '"v"', "h[0]"), ("k977", '"s"', "k977")]
+    elif mode == "red":
+        ins += [(nm, '"v"', nm) for nm in ("prevhi", "init", "hj")] + [("k977", '"s"', "k977")]
+    if addend:
+        ins.append(("ej", '"v"', "ej"))
+    for pr in pairs:
+        for nm in pr:
+            if ("L" + nm) not in [k for k, _, _ in ins]:
+                ins.append(("L" + nm, '"v"', nm))
+    key = {k: f"%{n}" for n, (k, _, _) in enumerate(outs + ins)}
+    acc = key["acc"]
+    lines = []
+    if mode == "red0":
+        lines.append(f"v_mad_u64_u32 {acc}, {key['c0']}, {key['h0']}, {key['k977']}, 0")
+    elif mode == "red":
+        lines.append(f"v_mad_u64_u32 {acc}, {key['c0']}, {key['prevhi']}, 1, {key['init']}")
+        lines.append(f"v_mad_u64_u32 {acc}, {key['c0']}, {key['hj']}, {key['k977']}, {acc}")
+    if addend:
+        lines.append(f"v_mad_u64_u32 {acc}, {key['c0']}, {key['ej']}, 1, {acc}")
+    m, seq = len(pairs), []
+    for p in range(m):
+        seq.append(("mad", p))
+        if p - 2 >= 0:
+            seq.append(("add", p - 2))
+    for p in range(max(0, m - 2), m):
+        seq.append(("add", p))
+    emitted, first_add = {}, True
+    for kind, p in seq:
+        c = key["rk"] if classes[p] == "check" else key[f"c{p % 3}"]
+        if kind == "mad":
+            x, y = pairs[p]
+            lines.append(f"v_mad_u64_u32 {acc}, {c}, {key['L' + x]}, {key['L' + y]}, {acc}")
+            emitted[p] = len(lines) - 1
+        elif classes[p] == "add":
+            dist = len(lines) - 1 - emitted[p]
+            if dist < 2:
+                lines.append(f"s_nop {1 - dist}")
+            lines.append(f"v_addc_co_u32_e64 {key['top']}, {c}, {'0' if first_add else key['top']}, 0, {c}")
+            first_add = False
+    asm = "\\n\\t".join(lines)
+    text = (f'  asm("{asm}"\n      : ' + ", ".join(f"{cons}({cx})" for _, cons, cx in outs) + "\n      : " +
+            ", ".join(f"{cons}({cx})" for _, cons, cx in ins) + ");")
+    return text, not has_add, kept + int(has_check)
+
+
+def rare_or(n):
+    """The scan's rare mask: the n kept carry pairs OR-ed by the scalar unit
+    after the last column. The last of them was written by column 7's first
+    product, seven mads and seven v_addc before: well past the two
+    instructions that a reader of a VALU-written SGPR pair keeps."""
+    lines = ["s_or_b64 %0, %1, %2"] + [f"s_or_b64 %0, %0, %{j}" for j in range(3, n + 1)]
+    return ('  asm("' + "\\n\\t".join(lines) + '"\n      : "=&s"(rare)\n      : ' +
+            ", ".join(f'"s"(rk{j})' for j in range(n)) + '\n      : "scc");')
+
+
+FAST_DOC = ["fast form: no v_addc for a column's first product. Returns the rare mask, one",
+            "bit per lane whose first full product of some column carried; r and T are",
+            "the exact form's whenever the mask is 0 (tools/gen_mul_asm.py ColumnBounds)."]
+SCHEDULES = {}   # fast form -> [(column, [(x, y, class)])] in scan order
+
+
+def fast_column(name, bounds, pairs, k, mode, addend, state):
+    """One column of a fast scan: bounds, classes, asm. state: {"rare": carry
+    pairs kept so far}. -> (asm text, the column's top = 0 at the C level)"""
+    if mode == "acc":
+        bounds.high_start()
+    else:
+        bounds.low_start(mode == "red0", addend)
+    order, cls = bounds.classify(pairs)
+    # only the first column (acc = 0, then at once near 2^64) takes a v_addc without a check before it
+    assert cls.count("check") <= 1 and (k == 8 or "check" in cls or "add" not in cls), (name, k)
+    SCHEDULES.setdefault(name, []).append((k, [pr + (c,) for pr, c in zip(order, cls)]))
+    text, notop, state["rare"] = fast_block(order, cls, mode, addend, state["rare"])
+    return text, notop
+
+
+def reduced_scan(name, cols, doc, addend=False, fast=False):
     """A 256x256 product given as column pair lists cols[0..14], reduced mod p
     on the fly: columns 8..14 are scanned first (their carry-in from column 7
     is deferred), giving the high half h[0..7]; columns 0..7 then fold
@@ -134,11 +294,14 @@ def reduced_scan(name, cols, doc, addend=False):
     h[j-1] enter column j). Output: r[0..7] and T < 2^38 with
     a * b == r + T * 2^256 (mod p)."""
     sig = "uint32_t r[8], uint64_t& T, const uint32_t* a, const uint32_t* b" + (", const uint32_t* e" if addend else "")
+    if fast:
+        exact, name, doc = name, name + "_fc", [f"{name}, " + FAST_DOC[0]] + FAST_DOC[1:]
+        bounds, state = ColumnBounds(), {"rare": 0}
     out = [""] + ["// " + l for l in doc] + [
-        f"__device__ __forceinline__ void {name}({sig}) {{",
+        f"__device__ __forceinline__ {'uint64_t' if fast else 'void'} {name}({sig}) {{",
         "  uint64_t acc = 0;",
         "  uint32_t top;",
-        "  uint64_t c0, c1, c2;",
+        "  uint64_t c0, c1, c2" + (", rare, @RK@;" if fast else ";"),
         "  uint32_t h[8], o[8];",
         "  const uint32_t k977 = 977u;"]
     if "sqr" in name:
@@ -153,7 +316,12 @@ def reduced_scan(name, cols, doc, addend=False):
                 "  d[8] = a[7] >> 31;"]
     for k in range(8, 15):
         out.append(f"  // column {k}: {len(cols[k])} products")
-        out.append(scan_block(cols[k], "acc"))
+        if fast:
+            blk, notop = fast_column(name, bounds, cols[k], k, "acc", False, state)
+            out.append(blk)
+            out += ["  top = 0;"] * notop
+        else:
+            out.append(scan_block(cols[k], "acc"))
         out.append(f"  h[{k - 8}] = (uint32_t)acc;")
         out.append("  acc = (acc >> 32) | ((uint64_t)top << 32);")
     out.append("  h[7] = (uint32_t)acc;  // the high half is < 2^256: nothing above")
@@ -170,6 +338,9 @@ def reduced_scan(name, cols, doc, addend=False):
             blk = scan_block(cols[j], "rede" if addend else "red")
         else:
             blk = scan_block(cols[j], "red0e" if addend else "red0")
+        if fast:
+            blk, notop = fast_column(name, bounds, cols[j], j, "red" if j else "red0", addend, state)
+            blk += "\n  top = 0;" * notop
         out.append("  " + blk.replace("\n", "\n  "))
         out.append("    acc = accn;")
         out.append("  }")
@@ -179,6 +350,11 @@ def reduced_scan(name, cols, doc, addend=False):
     out.append("#pragma unroll")
     out.append("  for (int j = 0; j < 8; ++j) r[j] = o[j];")
     out.append("  (void)c0; (void)c1; (void)c2;")
+    if fast:
+        assert 2 <= state["rare"] <= 14
+        out.append(rare_or(state["rare"]))
+        out = [l.replace("@RK@", ", ".join(f"rk{j}" for j in range(state["rare"]))) for l in out]
+        out.append("  return rare;")
     out.append("}")
     return out
 
@@ -205,10 +381,13 @@ def reduced_functions():
         "a^2 mod p as a column scan of 43 products (8 squares, 7 a_i * 2a_{i+1},",
         "28 a_i * (2a)_j limbs incl. the 1-bit limb 8) instead of 36 products plus",
         "a shift-and-add pass over 16 words, with the same folded reduction."])
+    out += reduced_scan("mul256_red_ps", mul_cols, [], fast=True)
+    out += reduced_scan("mul256_red_add_ps", mul_cols, [], addend=True, fast=True)
+    out += reduced_scan("sqr256_red_ps", sqr_cols[:15], [], fast=True)
     return out
 
 
-def reduced_sum_scan(name, sig, cols, preps, doc):
+def reduced_sum_scan(name, sig, cols, preps, doc, fast=False):
     """A sum of two 256x256 products, a * b + c * d, given as the concatenated
     column pair lists of both terms (cols[k] = term 1's column k + term 2's),
     scanned into one set of accumulators and reduced once, as reduced_scan.
@@ -223,18 +402,26 @@ def reduced_sum_scan(name, sig, cols, preps, doc):
     low columns: 2 (k + 1) products of < 2^64 in column k) and H < 2^257,
     so T < 2^36 + 15 + 2 C + 1 < 2^37, below fe_fold_top's 2^40; the largest T,
     at all four operands 2^256 - 1, is 2^36 + 2^33 + 1935."""
+    if fast:
+        name, doc = name + "_fc", [f"{name}, " + FAST_DOC[0]] + FAST_DOC[1:]
+        bounds, state = ColumnBounds(), {"rare": 0}
     out = [""] + ["// " + l for l in doc] + [
-        f"__device__ __forceinline__ void {name}({sig}) {{",
+        f"__device__ __forceinline__ {'uint64_t' if fast else 'void'} {name}({sig}) {{",
         "  uint64_t acc = 0;",
         "  uint32_t top;",
-        "  uint64_t c0, c1, c2;",
+        "  uint64_t c0, c1, c2" + (", rare, @RK@;" if fast else ";"),
         "  uint32_t h[9], o[8];",
         "  const uint32_t k977 = 977u;"]
     for pr in preps:
         out += sqr_prep(*pr)
     for k in range(8, 15):
         out.append(f"  // column {k}: {len(cols[k])} products")
-        out.append(scan_block(cols[k], "acc"))
+        if fast:
+            blk, notop = fast_column(name, bounds, cols[k], k, "acc", False, state)
+            out.append(blk)
+            out += ["  top = 0;"] * notop
+        else:
+            out.append(scan_block(cols[k], "acc"))
         out.append(f"  h[{k - 8}] = (uint32_t)acc;")
         out.append("  acc = (acc >> 32) | ((uint64_t)top << 32);")
     out.append("  const uint64_t h78 = acc;  // h[7] + h[8] * 2^32")
@@ -251,6 +438,9 @@ def reduced_sum_scan(name, sig, cols, preps, doc):
             blk = scan_block(cols[j], "red")
         else:
             blk = scan_block(cols[j], "red0")
+        if fast:
+            blk, notop = fast_column(name, bounds, cols[j], j, "red" if j else "red0", False, state)
+            blk += "\n  top = 0;" * notop
         out.append("  " + blk.replace("\n", "\n  "))
         out.append("    acc = accn;")
         out.append("  }")
@@ -261,11 +451,20 @@ def reduced_sum_scan(name, sig, cols, preps, doc):
     out.append("#pragma unroll")
     out.append("  for (int j = 0; j < 8; ++j) r[j] = o[j];")
     out.append("  (void)c0; (void)c1; (void)c2;")
+    if fast:
+        assert 2 <= state["rare"] <= 14
+        out.append(rare_or(state["rare"]))
+        out = [l.replace("@RK@", ", ".join(f"rk{j}" for j in range(state["rare"]))) for l in out]
+        out.append("  return rare;")
     out.append("}")
     return out
 
 
 def reduced_sum_functions():
+    return reduced_sum_functions_(False) + reduced_sum_functions_(True)
+
+
+def reduced_sum_functions_(fast):
     ab, cd = col_lists("mul", "a", "b"), col_lists("mul", "c", "d")
     aa = col_lists("sqr", "a", ("ea", "da"))
     assert max(len(x) + len(y) for x, y in zip(ab, cd)) == 16
@@ -277,13 +476,13 @@ def reduced_sum_functions():
          "limb products of both terms into the same accumulators, so the two terms",
          "share one folded reduction (mul256_red_ps) and one top fold. The high half",
          "has a ninth limb h[8] (0 or 1), folded into T. Output: r[0..7] and T < 2^37",
-         "with a * b + c * d == r + T * 2^256 (mod p)."])
+         "with a * b + c * d == r + T * 2^256 (mod p)."], fast=fast)
     out += reduced_sum_scan(
         "sqrmul256_red_sum_ps",
         "uint32_t r[8], uint64_t& T, const uint32_t* a, const uint32_t* c, const uint32_t* d",
         [x + y for x, y in zip(aa, cd)], [("a", "ea", "da")],
         ["a^2 + c * d mod p in one product scan: the 43-product square lists of",
-         "sqr256_red_ps and the 64 products of c * d, one folded reduction."])
+         "sqr256_red_ps and the 64 products of c * d, one folded reduction."], fast=fast)
     return out
 
 
@@ -448,7 +647,9 @@ def render():
     """The text of hkv_mul_asm.h."""
     out = ["// GENERATED by tools/gen_mul_asm.py — do not edit.",
            "// 256x256 -> 512-bit product, product scanning in gfx950 inline asm",
-           "// (one v_mad_u64_u32 + one v_addc_co_u32 per limb product).",
+           "// (one v_mad_u64_u32 per limb product and one v_addc_co_u32 for its carry; the",
+           "// *_fc fast forms have no v_addc for a column's first product and return a",
+           "// rare mask instead).",
            "#pragma once",
            "#include <stdint.h>",
            "",
@@ -508,7 +709,20 @@ def render():
     return "\n".join(out) + "\n"
 
 
+def fast_schedules():
+    """The fast forms' product order as data: {name: [(column, [(x, y, class)])]
+    in scan order} (tests/first_carry_model.py walks it)."""
+    SCHEDULES.clear()
+    render()
+    return {k: list(v) for k, v in SCHEDULES.items()}
+
+
 def main():
+    import sys
+    if sys.argv[1:] == ["--schedule"]:
+        import json
+        print(json.dumps(fast_schedules(), indent=1))
+        return
     open(OUT, "w").write(render())
     print("wrote", OUT)
 

@@ -3,6 +3,9 @@
 # the 1M headline and the configs[0] / configs[2] block legs, alternated.
 #   VARIANTS="maxilp memclause" TAG=r06r bash tools/gpu_ab_variants.sh
 # (haskoin-node_amd/lib/libhkv_<v>.so; "base" = the in-tree libhkv.so)
+# A source switch is a variant like any flag: the exact product scans everywhere,
+#   make -C haskoin-node_amd/csrc OUT=../lib/exact EXTRA=-DHKV_FIRST_CARRY=0 ../lib/exact/libhkv.so
+#   cp haskoin-node_amd/lib/exact/libhkv.so haskoin-node_amd/lib/libhkv_exact.so; VARIANTS=exact ...
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out

@@ -11,8 +11,12 @@
 // reduction), each against the 8 x 32-bit fe_mul / fe_sqr of the product.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/ubench_field.hip -o tools/ubench_field
-//        (-DHKV_MUL_ASM=0: the row-wise C product instead of the asm scanner)
+//        (ops 0, 1, 5, 6, 16, 17 ask for the fast scans, FC = true; -DHKV_FIRST_CARRY=0: the exact scans
+//        there too; `ubench_field fc`
+//        runs only the products, sums, pairs and group formulas, at 1 and 4
+//        waves per SIMD: the fast forms' A/B)
 #include <cstdio>
+#include <string>
 #include <vector>
 #include "../haskoin-node_amd/csrc/hkv_group.h"
 #include "fe29_proto.h"
@@ -63,9 +67,9 @@ __global__ void __launch_bounds__(256) kern(const uint32_t* in, uint32_t* out, S
   unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
   for (int it = 0; it < ITERS; ++it) {
     if constexpr (OP == 0) {
-      fe_mul(p.x, p.x, b);
+      fe_mul<true>(p.x, p.x, b);
     } else if constexpr (OP == 1) {
-      fe_sqr(p.x, p.x);
+      fe_sqr<true>(p.x, p.x);
     } else if constexpr (OP == 2) {
       fe_mul(p.x, p.x, b);
       fe_mul(p.y, p.y, b);
@@ -74,16 +78,20 @@ __global__ void __launch_bounds__(256) kern(const uint32_t* in, uint32_t* out, S
     } else if constexpr (OP == 4) {
       fe_sub(p.x, p.x, b);
     } else if constexpr (OP == 5) {
-      gej_double(p, p);
+      gej_double<true>(p, p);
     } else if constexpr (OP == 6) {
       bool hz, rz;
-      gej_add_ge_core(p, p, p.z, b, p.y, hz, rz, nullptr);
+      gej_add_ge_core<true>(p, p, p.z, b, p.y, hz, rz, nullptr);
     } else if constexpr (OP == 11) {
       fe_mul2(p.x, p.x, b, p.y, p.y, b);
     } else if constexpr (OP == 12) {
       fe_sqr2(p.x, p.x, p.y, p.y);
     } else if constexpr (OP == 13) {
       fe_sqrmul(p.x, p.x, p.y, p.y, b);
+    } else if constexpr (OP == 16) {
+      fe_mul_sum<true>(p.x, p.x, b, p.y, p.z);
+    } else if constexpr (OP == 17) {
+      fe_sqrmul_sum<true>(p.x, p.x, b, p.y);
     } else if constexpr (OP == 14) {
       fe_mul_ref(p.x, p.x, b);
     } else if constexpr (OP == 15) {
@@ -129,7 +137,8 @@ static const char* NAMES[] = {"fe_mul", "fe_sqr", "fe_mul x2 (independent)", "fe
                               "gej_add_ge (mixed)", "fe29_mul", "fe29_sqr", "fe29_sub+carry",
                               "fp52_mul (product only, lower bound)", "fe_mul2 (interleaved pair)",
                               "fe_sqr2 (interleaved pair)", "fe_sqrmul (interleaved pair)",
-                              "fe_mul_ref (512-bit product + fe_reduce512)", "fe_sqr_ref (512-bit square + fe_reduce512)"};
+                              "fe_mul_ref (512-bit product + fe_reduce512)", "fe_sqr_ref (512-bit square + fe_reduce512)",
+                              "fe_mul_sum", "fe_sqrmul_sum"};
 
 template <int OP>
 void run(int n_cu, int blocks_per_cu) {
@@ -281,7 +290,8 @@ __global__ void check_pairs(uint32_t* bad) {
   if (nb) atomicAdd(bad, nb);
 }
 
-int main() {
+int main(int argc, char** argv) {
+  const bool fc_only = argc > 1 && std::string(argv[1]) == "fc";
   hipDeviceProp_t p;
   hipGetDeviceProperties(&p, 0);
   const int n_cu = p.multiProcessorCount;
@@ -299,12 +309,20 @@ int main() {
     printf("{\"check\": \"fe_inv / 64 squarings / cneg / mixed chain vs the reference ops (bit mask of failing checks)\", \"lanes\": %d, \"fail_mask\": %u}\n", 64 * 256, hb);
     hipFree(bad);
   }
+  if (fc_only) {
+    printf("{\"first_carry\": %d}\n", (int)HKV_FIRST_CARRY);
+    for (int bpc : {1, 4}) {
+      run<0>(n_cu, bpc); run<1>(n_cu, bpc); run<16>(n_cu, bpc); run<17>(n_cu, bpc);
+      run<11>(n_cu, bpc); run<12>(n_cu, bpc); run<13>(n_cu, bpc); run<5>(n_cu, bpc); run<6>(n_cu, bpc);
+    }
+    return 0;
+  }
   for (int bpc : {1, 2, 4}) {
     run<0>(n_cu, bpc); run<1>(n_cu, bpc); run<2>(n_cu, bpc); run<3>(n_cu, bpc);
     run<4>(n_cu, bpc); run<5>(n_cu, bpc); run<6>(n_cu, bpc);
     run<7>(n_cu, bpc); run<8>(n_cu, bpc); run<9>(n_cu, bpc); run<10>(n_cu, bpc);
     run<11>(n_cu, bpc); run<12>(n_cu, bpc); run<13>(n_cu, bpc);
-    run<14>(n_cu, bpc); run<15>(n_cu, bpc);
+    run<14>(n_cu, bpc); run<15>(n_cu, bpc); run<16>(n_cu, bpc); run<17>(n_cu, bpc);
   }
   return 0;
 }
