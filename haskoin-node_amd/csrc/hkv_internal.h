@@ -84,6 +84,16 @@ enum {
   HKV_DBG_FC_MUL_SUM = 49,      // as op 38
   HKV_DBG_FC_SQRMUL_SUM = 50,   // as op 39
   HKV_DBG_FC_MUL_MASK = 51,     // op 46's whole rare mask of the lane's wave in out[0..2) (every active lane writes it)
+  // The joint radix-8 digits (hkv_joint_digits.h), built whatever
+  // HKV_JOINT_DIGITS selects for the chain launch.
+  // a = |k1| (limbs 0..4, < 2^129) and limb 5 bit 0 its sign, b = k2 alike:
+  // the lane forms the Booth digit words hkv_glv_kernel writes and runs the
+  // chain launch's preamble on them; out[0..11) = the packed codes.
+  HKV_DBG_JOINT_RECODE = 52,
+  // a = a scalar k (not 0), b's low limb = j (0..10). The lane runs the joint
+  // table build on Q = k G and returns entry j made affine on Q's curve: out =
+  // x | y, normalised.
+  HKV_DBG_JOINT_TABLE = 53,
   // Group ops (hkv_debug_group_kernel): lane i takes rows 2i and 2i + 1 (n
   // even, n / 2 lanes). a: k1 | z1, b: k2 | w. The lane's points are
   // P1 = k1 G and P2 = k2 G (ecmult_simple; a zero scalar is infinity), P1

@@ -14,7 +14,9 @@
 //      (only the paired-form instance, ILP = true, remains; above the
 //      mid-size range the same two phases run as two launches, 2a:
 //      hkv_qtable_kernel then hkv_chain_kernel, over per-signature tables,
-//      with the plain forms); it leaves
+//      with the plain forms, and on joint radix-8 digits over Z[lambda]:
+//      an 11-entry table, 44 windows of 3 doublings and one addition,
+//      hkv_joint_digits.h); it leaves
 //      B' = u2*Q' to
 //   2b. hkv_finish_kernel, hkv_rare_kernel, hkv_yverdict_kernel — u1*G from
 //      per-window tables, y0 = num/den from "x(u1 G + u2 Q) == r", and the
@@ -35,6 +37,7 @@
 #include "hkv_group.h"
 #include "hkv_hash.h"
 #include "hkv_layout.h"
+#include "hkv_joint_digits.h"
 #include "hkv_internal.h"
 #include "hkv_sighash_dev.h"
 #include "hkv_tail_plan.h"
@@ -636,6 +639,131 @@ HKV_DEV void qtable_build(const ge& q, uint32_t* __restrict__ qs, uint32_t n_lan
   }
 }
 
+// The joint form of the table launch (hkv_joint_digits.h, hkv_layout.h JQ_*):
+// the 11 entries (a + b lambda) Q' of the joint digits' orbits, x | y only, in
+// the Booth table's 48 quads per signature. The walk is the Booth one: entry j
+// is entry j - 1 plus a unit image (beta^e x, +-y) of Q', read back from entry
+// 0 at each step, and pass 2 rescales every entry to the last one's Z. The
+// nine z-ratios H_2..H_10 wait between the passes where nothing else lives:
+// four in LDS (idle in this launch: 32 KiB per workgroup, four workgroups per
+// CU), two in the lane's 4 spare quads, one in its Zg slot (written after the
+// build) and two in entry 10's slot, whose raw x, y stay in registers until
+// pass 2 has read them. A sum of two of these small multiples of Q' vanishes
+// only for a key of small order on a twist, whose verdict is reject whatever
+// the table holds.
+typedef uint32_t JqLds[4][8][WG];
+HKV_DEV uint4* jq_ptr(uint32_t* qs, uint32_t n_lanes, uint32_t lane, int entry, int c) {
+  return reinterpret_cast<uint4*>(qs) + ((size_t)entry * n_lanes + lane) * JQ_QUADS_PER_ENTRY + c;
+}
+HKV_DEV void quads_store(uint4* p, const fe& a) {
+  p[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+  p[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+HKV_DEV void quads_load(const uint4* p, fe& a) {
+  const uint4 v0 = p[0], v1 = p[1];
+  a.v[0] = v0.x; a.v[1] = v0.y; a.v[2] = v0.z; a.v[3] = v0.w;
+  a.v[4] = v1.x; a.v[5] = v1.y; a.v[6] = v1.z; a.v[7] = v1.w;
+}
+HKV_DEV void jq_load(const uint32_t* __restrict__ qs, uint32_t n_lanes, uint32_t lane, int entry, int c, fe& a) {
+  quads_load(jq_ptr(const_cast<uint32_t*>(qs), n_lanes, lane, entry, c), a);
+}
+struct JqPark {
+  JqLds* lds;
+  uint4 *spare, *zslot, *last;  // 4 quads, 2 quads, entry 10's 4 quads
+  // slot h = j - 2 of H_j (h is uniform)
+  HKV_DEV uint4* quads(int h) const { return h < 6 ? spare + 2 * (h - 4) : h == 6 ? zslot : last + 2 * (h - 7); }
+  HKV_DEV void store(int h, const fe& a) const {
+    if (h < 4) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) (*lds)[h][k][threadIdx.x] = a.v[k];
+    } else {
+      quads_store(quads(h), a);
+    }
+  }
+  HKV_DEV void load(int h, fe& a) const {
+    if (h < 4) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a.v[k] = (*lds)[h][k][threadIdx.x];
+    } else {
+      quads_load(quads(h), a);
+    }
+  }
+};
+// zslot: the lane's Zg slot (the caller writes Zg there after the build)
+HKV_DEV void qtable_build_joint(const ge& q, uint32_t* __restrict__ qs, uint32_t n_lanes, uint32_t lane, uint4* zslot,
+                                JqLds* lds, fe& Zg) {
+  static_assert(JD_ENTRIES == JQ_ENTRIES, "one entry per orbit");
+  const JqPark park = {lds, reinterpret_cast<uint4*>(qs) + (size_t)JQ_ENTRIES * JQ_QUADS_PER_ENTRY * n_lanes +
+                                (size_t)lane * JQ_SPARE_QUADS,
+                       zslot, jq_ptr(qs, n_lanes, lane, JQ_ENTRIES - 1, 0)};
+  gej p2, pj;
+  gej_set_ge(p2, q);
+  gej_double(p2, p2);  // 2Q (Jacobian, scale Z2)
+  {
+    fe z2, qx, qy;  // Q' = phi_Z2(Q) = (x Z2^2, y Z2^3)
+    fe_sqr(z2, p2.z);
+    fe_mul(qx, q.x, z2);
+    fe_mul(z2, z2, p2.z);
+    fe_mul(qy, q.y, z2);
+    quads_store(jq_ptr(qs, n_lanes, lane, 0, 0), qx);
+    quads_store(jq_ptr(qs, n_lanes, lane, 0, 2), qy);
+  }
+  quads_store(jq_ptr(qs, n_lanes, lane, 1, 0), p2.x);
+  quads_store(jq_ptr(qs, n_lanes, lane, 1, 2), p2.y);
+  pj.x = p2.x;
+  pj.y = p2.y;
+  fe_set_u32(pj.z, 1);
+#pragma unroll 1
+  for (int j = 2; j < JQ_ENTRIES; ++j) {
+    // entry j = entry j - 1 + (-1)^s lambda^e Q' (uniform in j)
+    const uint32_t e = (JD_STEP_E >> (2 * (j - 1))) & 3u;
+    const bool neg = ((JD_STEP_S >> (j - 1)) & 1u) != 0;
+    bool hz, rz;
+    fe h, tx, ty;
+    jq_load(qs, n_lanes, lane, 0, 0, tx);
+    if (e != 0u) {
+      fe beta, bx;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
+      fe_mul(bx, tx, beta);
+      if (e == 2u) {  // beta^2 x = -(x + beta x)
+        fe_add(bx, tx, bx);
+        fe_neg(bx, bx);
+      }
+      tx = bx;
+    }
+    jq_load(qs, n_lanes, lane, 0, 2, ty);
+    fe_cneg(ty, ty, neg);
+    gej_add_ge_core(pj, pj, pj.z, tx, ty, hz, rz, &h);
+    if (j < JQ_ENTRIES - 1) {  // (the last entry's x, y wait in pj)
+      quads_store(jq_ptr(qs, n_lanes, lane, j, 0), pj.x);
+      quads_store(jq_ptr(qs, n_lanes, lane, j, 2), pj.y);
+    }
+    park.store(j - 2, h);
+  }
+  fe_mul(Zg, p2.z, pj.z);  // total scale: phi_Z2 then phi_Zc, Zc = pj.z
+  fe rho;
+  fe_set_u32(rho, 1);
+#pragma unroll 1
+  for (int j = JQ_ENTRIES - 2; j >= 0; --j) {
+    fe x, y, t;
+    if (j >= 1) {
+      park.load(j - 1, t);  // H_{j+1}
+      fe_mul(rho, rho, t);
+    }
+    jq_load(qs, n_lanes, lane, j, 0, x);
+    jq_load(qs, n_lanes, lane, j, 2, y);
+    fe_sqr(t, rho);
+    fe_mul(x, x, t);
+    fe_mul(t, t, rho);
+    fe_mul(y, y, t);
+    quads_store(jq_ptr(qs, n_lanes, lane, j, 0), x);
+    quads_store(jq_ptr(qs, n_lanes, lane, j, 2), y);
+  }
+  quads_store(park.last, pj.x);
+  quads_store(park.last + 2, pj.y);
+}
+
 // The shared doubling chain of k1 * Q' + k2 * lambda(Q'), 33 radix-16 windows
 // from the top, over the lane's table: acc, inf = the sum B' on the table's
 // curve. Window w's digit word is loaded one window ahead, hiding its
@@ -703,6 +831,87 @@ HKV_DEV void q_chain(gej& acc, bool& inf, SoACView iv, uint32_t i, bool valid, c
     }
     nterm = 2;
     dw = dw_next;
+  }
+}
+
+// The chain on joint radix-8 digits (hkv_joint_digits.h), 2a's chain launch.
+// The preamble: the lane's signed k1, k2 rebuilt exactly from its Booth digit
+// words (word(w): window w's, low to high; sum_w d_w 16^w with a running
+// carry) and its GLV signs, then recoded into the lane's column of jd.
+template <class DigitWord>
+HKV_DEV void joint_digits_lane(uint32_t (*jd)[WG], uint32_t signs, DigitWord word) {
+  constexpr uint32_t QM = (1u << QW) - 1u;
+  uint32_t k1[5] = {0, 0, 0, 0, 0}, k2[5] = {0, 0, 0, 0, 0};
+  int c1 = 0, c2 = 0;
+#pragma unroll
+  for (int w = 0; w < NWIN; ++w) {
+    const uint32_t dw = word(w);
+    const int t1 = (int)(dw & QDIG_MASK) - QBIAS + c1, t2 = (int)((dw >> QDIG_BITS) & QDIG_MASK) - QBIAS + c2;
+    const uint32_t n1 = (uint32_t)t1 & QM, n2 = (uint32_t)t2 & QM;
+    c1 = (t1 - (int)n1) >> QW;
+    c2 = (t2 - (int)n2) >> QW;
+    const int q = (QW * w) >> 5, sh = (QW * w) & 31;  // (the magnitudes are below 2^129: word 4 at most)
+    k1[q] |= n1 << sh;
+    k2[q] |= n2 << sh;
+    if (sh + QW > 32 && q < 4) {
+      k1[q + 1] |= n1 >> (32 - sh);
+      k2[q + 1] |= n2 >> (32 - sh);
+    }
+  }
+  jd_signed(k1, (signs & 1u) != 0);
+  jd_signed(k2, (signs & 2u) != 0);
+  uint32_t out[JD_WORDS];
+  joint_recode(k1, k2, out);
+#pragma unroll
+  for (int q = 0; q < JD_WORDS; ++q) jd[q][threadIdx.x] = out[q];
+}
+// The window loop: from the highest window in which a lane of the wave has a
+// non-zero digit, three doublings and one addition of the digit's entry under
+// its unit: beta x by one product where a lane of the wave needs it (beta^2 x
+// = -(x + beta x) under the lane mask), y negated by s.
+HKV_DEV void q_chain_joint(gej& acc, bool& inf, const uint32_t (*jd)[WG], const uint32_t* __restrict__ qs,
+                           uint32_t n_lanes, uint32_t lane) {
+  inf = true;
+  fe_set_zero(acc.x);
+  fe_set_zero(acc.y);
+  fe_set_zero(acc.z);
+  int win = JD_WINDOWS - 1;
+#pragma unroll 1
+  while (win > 0 && !__any(((jd[win >> 2][threadIdx.x] >> (7 * (win & 3))) & JD_ENTRY_MASK) != JD_ZERO)) --win;
+  bool dbl = false;  // the first window starts from infinity: no doublings
+#pragma unroll 1
+  for (; win >= 0; --win) {
+    const uint32_t code = (jd[win >> 2][threadIdx.x] >> (7 * (win & 3))) & JD_CODE_MASK;
+    const uint32_t ent = code & JD_ENTRY_MASK;
+    const bool take = ent != JD_ZERO;
+    if (dbl) {
+#pragma unroll 1
+      for (int d = 0; d < 3; ++d) {
+        if (!inf) ec_double<false>(acc);
+      }
+    }
+    dbl = true;
+    const int ie = take ? (int)ent : 0;
+    const uint32_t e = (code >> JD_E_SHIFT) & 3u;
+    const bool e2 = take && e == 2u;
+    fe tx, ty;
+    jq_load(qs, n_lanes, lane, ie, 0, tx);
+    const bool e1 = take && e == 1u;
+    if (__any(e1 || e2)) {  // beta x by a product (the table keeps x | y); beta^2 x = -(x + beta x)
+      fe beta, bx;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
+      fe_mul<true>(bx, tx, beta);
+      fe_cmov(tx, bx, e1);
+      fe_add(bx, tx, bx);
+      fe_cmov(tx, bx, e2);
+      fe_cneg(tx, tx, e2);
+    }
+    jq_load(qs, n_lanes, lane, ie, 2, ty);
+    fe_cneg(ty, ty, (code >> JD_S_SHIFT) != 0u);
+    const bool was_inf = inf;
+    ec_accumulate<false>(acc, inf, acc.z, tx, ty, take);
+    if (__any(take && was_inf)) gej_accumulate_from_inf(acc, inf, tx, ty, take && was_inf);
   }
 }
 
@@ -799,6 +1008,11 @@ __global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict_
 //     may run in parts (hkv_layout.h HKV_REC_PART), two at a time on two
 //     streams, each in a slot of its own inside the chunk's scratch: the
 //     kernels take the slot's base as qs and the part as (i0, cn).
+//     With HKV_JOINT_DIGITS (hkv_layout.h, the default) the table launch
+//     builds the 11 entries (a + b lambda) Q' of hkv_joint_digits.h and the
+//     chain launch recodes its lane's Booth digits into joint radix-8 digits
+//     in LDS: 44 windows of three doublings and one addition (q_chain_joint)
+//     where the Booth chain (q_chain) runs 33 of four and two.
 // ---------------------------------------------------------------------------
 HKV_DEV uint4* zg_ptr(uint32_t* qs, uint32_t cn, uint32_t s) {
   return reinterpret_cast<uint4*>(qs) + (size_t)cn * QTAB_QUADS + (size_t)s * QTAB_ZG_QUADS;
@@ -815,8 +1029,13 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_qtable_kernel(const 
   ge q;
   lane_q(q, iv, i, valid);
   fe Zg;
-  qtable_build(q, qs, cn, s, Zg);
   uint4* z = zg_ptr(qs, cn, s);
+  if constexpr (JOINT_DIGITS) {
+    __shared__ JqLds park;
+    qtable_build_joint(q, qs, cn, s, z, &park, Zg);
+  } else {
+    qtable_build(q, qs, cn, s, Zg);
+  }
   z[0] = make_uint4(Zg.v[0], Zg.v[1], Zg.v[2], Zg.v[3]);
   z[1] = make_uint4(Zg.v[4], Zg.v[5], Zg.v[6], Zg.v[7]);
 }
@@ -826,8 +1045,10 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_chain_kernel(uint32_
                                                                       const uint32_t* __restrict__ qs,
                                                                       unsigned long long* __restrict__ clk) {
   // the lane's GLV signs, read once per term (q_chain): held in a register
-  // they were spilled to scratch at 128 VGPRs; LDS is idle in this kernel
-  __shared__ uint32_t signs[WG];
+  // they were spilled to scratch at 128 VGPRs; LDS is idle in this kernel.
+  // The joint form keeps the lane's 44 digit codes there instead (11 KiB per
+  // workgroup): each lane reads only its own column, so no barrier.
+  __shared__ uint32_t lds[JOINT_DIGITS ? JD_WORDS : 1][WG];
   // optional clock probe (hkv_profile_clock), as in hkv_ecmult_kernel
   clock_probe(clk, 0);
   const uint32_t s = blockIdx.x * WG + threadIdx.x;  // < cn: the grid is cn / WG blocks
@@ -835,10 +1056,18 @@ __global__ void __launch_bounds__(WG, HKV_ECMULT_WAVES) hkv_chain_kernel(uint32_
   // (im indexed here, not through a view held by this body: see the view's header)
   const uint32_t flags = im[(size_t)IM_FLAGS.off * n_pad + i];
   const bool valid = (i < n) && (flags & FLAG_VALID);
-  signs[threadIdx.x] = ((flags & FLAG_NEG1) ? 1u : 0u) | ((flags & FLAG_NEG2) ? 2u : 0u);
+  const uint32_t sg = ((flags & FLAG_NEG1) ? 1u : 0u) | ((flags & FLAG_NEG2) ? 2u : 0u);
   gej acc;
   bool inf;
-  q_chain<false>(acc, inf, SoACView{im, n_pad}, i, valid, qs, cn, s, signs[threadIdx.x]);
+  if constexpr (JOINT_DIGITS) {
+    joint_digits_lane(lds, sg, [&](int w) {
+      return valid ? im[(size_t)(IM_DIG.off + w) * n_pad + i] : DIG_ZERO;
+    });
+    q_chain_joint(acc, inf, lds, qs, cn, s);
+  } else {
+    lds[0][threadIdx.x] = sg;
+    q_chain<false>(acc, inf, SoACView{im, n_pad}, i, valid, qs, cn, s, lds[0][threadIdx.x]);
+  }
 
   // hand B' = (X, Y, Z acc * Zg) on E_w to the finish kernel
   fe Zg, zt;
@@ -2750,6 +2979,48 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
       res[8] = (uint32_t)T;
       res[9] = (uint32_t)(T >> 32);
       res[10] = (uint32_t)(rare >> (threadIdx.x & 63u)) & 1u;
+      break;
+    }
+    case HKV_DBG_JOINT_RECODE: {
+      __shared__ uint32_t jd[JD_WORDS][WG];
+      uint32_t S1[5], S2[5], dig[NWIN];
+      for (int k = 0; k < 5; ++k) { S1[k] = x.v[k]; S2[k] = y.v[k]; }
+      uint32_t p1 = 0, p2 = 0;  // (write_qdigits' digits, kept in registers)
+#pragma unroll
+      for (int w = 0; w < NWIN; ++w) {
+        constexpr uint32_t QM = (1u << QW) - 1u;
+        const uint32_t v1 = p1 | ((S1[0] & QM) << 1), v2 = p2 | ((S2[0] & QM) << 1);
+        p1 = (S1[0] >> (QW - 1)) & 1u;
+        p2 = (S2[0] >> (QW - 1)) & 1u;
+        shr_bits<5>(S1, QW);
+        shr_bits<5>(S2, QW);
+        const int d1 = (int)((v1 + 1u) >> 1) - (int)((v1 >> QW) << QW);
+        const int d2 = (int)((v2 + 1u) >> 1) - (int)((v2 >> QW) << QW);
+        dig[w] = (uint32_t)(d1 + QBIAS) | ((uint32_t)(d2 + QBIAS) << QDIG_BITS);
+      }
+      joint_digits_lane(jd, (x.v[5] & 1u) | ((y.v[5] & 1u) << 1), [&](int w) { return dig[w]; });
+      for (int k = 0; k < JD_WORDS; ++k) res[k] = jd[k][threadIdx.x];
+      break;
+    }
+    case HKV_DBG_JOINT_TABLE: {
+      __shared__ JqLds park;
+      uint32_t tab[(QTAB_QUADS + QTAB_ZG_QUADS) * 4];  // the lane's table and Zg slot: n_lanes = 1, lane 0
+      ge g, q;
+      sc zero;
+      for (int k = 0; k < 8; ++k) zero.v[k] = 0;
+      ge_set_g(g);
+      if (!ecmult_simple(q, u, zero, g)) q = g;
+      fe Zg, zi, zi2, t;
+      qtable_build_joint(q, tab, 1u, 0u, reinterpret_cast<uint4*>(tab) + QTAB_QUADS, &park, Zg);
+      const int j = (int)(y.v[0] & 15u) < JD_ENTRIES ? (int)(y.v[0] & 15u) : 0;
+      jq_load(tab, 1u, 0u, j, 0, x);
+      jq_load(tab, 1u, 0u, j, 2, z);
+      fe_inv(zi, Zg);
+      fe_sqr(zi2, zi);
+      fe_mul(x, x, zi2);
+      fe_mul(t, zi2, zi);
+      fe_mul(z, z, t);
+      norm_pair(x, z);
       break;
     }
     default: break;

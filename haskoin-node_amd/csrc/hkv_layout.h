@@ -24,12 +24,21 @@ constexpr int REC_WORDS = REC_SIZE / 4;
 #ifndef HKV_GTAB_W
 #define HKV_GTAB_W 20
 #endif
+// The table-and-chain shape's chain (hkv_kernels.hip 2a) on joint radix-8
+// digits over Z[lambda] (hkv_joint_digits.h): 129 doublings and 44 additions
+// from an 11-entry table, where the Booth chain runs 124 and 66 from 8
+// entries. A form of the radix-16 layout only. 0: the Booth chain (the A/B).
+#ifndef HKV_JOINT_DIGITS
+#define HKV_JOINT_DIGITS (HKV_QW == 4)
+#endif
 constexpr int QW = HKV_QW;                       // Booth radix 2^QW of the k1 / k2 windows
 static_assert(QW == 4 || QW == 5, "radix-16 or radix-32 Q windows");
 constexpr int GTAB_W = HKV_GTAB_W;            // Booth radix of the fixed-base tables
 static_assert(GTAB_W % QW == 0 && GTAB_W >= 8 && GTAB_W <= 28, "G windows sit on Q window boundaries");
 constexpr int NWIN = (130 + QW - 1) / QW;        // 33 / 26: |k| < 2^129 plus the Booth carry
 constexpr int QBIAS = 1 << (QW - 1);             // digit range -QBIAS..QBIAS
+constexpr bool JOINT_DIGITS = HKV_JOINT_DIGITS != 0;
+static_assert(!JOINT_DIGITS || QW == 4, "the joint digits are rebuilt from radix-16 Booth digits");
 constexpr int QDIG_BITS = QW + 1;                // width of a biased digit in the digit word
 constexpr uint32_t QDIG_MASK = (1u << QDIG_BITS) - 1u;
 constexpr int GWIN = (128 + GTAB_W) / GTAB_W;  // covers 129 bits with the Booth carry
@@ -187,6 +196,16 @@ constexpr size_t GTAB_DWORDS = (size_t)GTAB_TABLES * GTAB_ENTRIES * 16;
 constexpr int QTAB_ENTRIES = QBIAS;
 constexpr int QTAB_QUADS_PER_ENTRY = 6;
 constexpr int QTAB_QUADS = QTAB_ENTRIES * QTAB_QUADS_PER_ENTRY;
+// The joint form of the table launch (HKV_JOINT_DIGITS, hkv_joint_digits.h)
+// keeps its 11 entries (a + b lambda) Q' in the same QTAB_QUADS quads per
+// signature, so the scratch and the plan do not change: per entry 4 quads,
+// x(2) | y(2), entry e of lane L at quad (e * n_lanes + L) * 4; the chain forms
+// beta * x by one product per window. The 4 quads per lane left over, at quad
+// 44 n_lanes + 4 L, park z-ratios during the build (hkv_kernels.hip).
+constexpr int JQ_ENTRIES = 11;
+constexpr int JQ_QUADS_PER_ENTRY = 4;
+constexpr int JQ_SPARE_QUADS = QTAB_QUADS - JQ_ENTRIES * JQ_QUADS_PER_ENTRY;
+static_assert(!JOINT_DIGITS || JQ_SPARE_QUADS == 4, "the joint table and two parked z-ratios fill the Booth table's quads");
 
 // Record batches above half the resident grid (hkv_kernels.hip 2a) build the
 // tables in one launch and run the chains in the next, over chunks of at most
