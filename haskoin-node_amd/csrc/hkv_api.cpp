@@ -155,6 +155,7 @@ struct DevCtx {
   DevBuf<uint64_t> spd_sums;
   DevBuf<uint8_t> spd_flags;
   uint32_t spend_stages = hkv::SPEND_STAGE_ALL;  // hkv_debug_spend_stages: the launches later calls run
+  uint32_t chain_stages = hkv::CHAIN_STAGE_ALL;  // hkv_debug_chain_stages: likewise
   // multisig inputs (hkv_sighash.hip section 4, hkv_kernels.hip 2e): desc
   // words, offsets, candidate and key-check verdict words, the candidate then
   // the key records; the host form's verdict words
@@ -2084,6 +2085,157 @@ int hkv_verify_block_txs_spends(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t
   const HostSpends sp{max_money, input_spender, tx_sums, tx_flags};
   return verify_block_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid,
                                tx_verdict_bits, input_first, input_src, input_cap, &sp);
+}
+
+// ---- header chain context: hkv_chain_context_device, hkv_connect_headers* -------
+
+namespace {
+// hkv_chain_ctx as the kernels take it; HKV_E_ARG for a context the rule does
+// not cover
+int chain_ctx_of(const hkv_chain_ctx* c, size_t n, hkv::ChainCtx& x) {
+  if (!c || c->height0 == 0 || (uint64_t)c->height0 + n > 0xFFFFFFFFull || c->n_prev_times < 1 ||
+      c->n_prev_times > hkv::CHAIN_MTP_SPAN || c->interval == 0 || c->target_timespan < 4 ||
+      c->target_timespan >= hkv::CHAIN_MAX_TIMESPAN)
+    return HKV_E_ARG;
+  x.height0 = c->height0;
+  x.n_prev_times = c->n_prev_times;
+  for (uint32_t j = 0; j < hkv::CHAIN_MTP_SPAN; ++j) x.prev_times[j] = c->prev_times[j];
+  x.parent_bits = c->parent_bits;
+  x.period_first_time = c->period_first_time;
+  x.period_real_bits = c->period_real_bits;
+  x.now = c->now;
+  for (int j = 0; j < 8; ++j) {
+    x.parent_work[j] = x.pow_limit[j] = 0;
+    for (int b = 3; b >= 0; --b) {
+      x.parent_work[j] = (x.parent_work[j] << 8) | c->parent_work[4 * j + b];
+      x.pow_limit[j] = (x.pow_limit[j] << 8) | c->pow_limit[4 * j + b];
+    }
+  }
+  x.limit_bits = hkv::cc_encode_compact(x.pow_limit);
+  x.interval = c->interval;
+  x.target_timespan = c->target_timespan;
+  x.min_diff_spacing = c->min_diff_spacing;
+  x.bip34_height = c->bip34_height;
+  x.bip66_height = c->bip66_height;
+  x.bip65_height = c->bip65_height;
+  x.flags = c->flags;
+  return HKV_OK;
+}
+
+bool chain_ptrs_ok(const uint8_t* d_headers, const uint8_t* d_hashes, const uint32_t* d_cp_heights,
+                   const uint8_t* d_cp_hashes, size_t n_cp, const uint32_t* d_mtp, const uint32_t* d_bits,
+                   const uint8_t* d_work, const uint8_t* d_status, const uint32_t* d_scratch) {
+  return d_headers && d_mtp && d_bits && d_work && d_status && d_scratch && n_cp <= 0xFFFFFFFFull &&
+         (n_cp == 0 || (d_hashes && d_cp_heights && d_cp_hashes)) && aligned(d_headers, 4) && aligned(d_hashes, 16) &&
+         aligned(d_cp_heights, 4) && aligned(d_cp_hashes, 4) && aligned(d_mtp, 4) && aligned(d_bits, 4) &&
+         aligned(d_work, 16) && aligned(d_scratch, 4);
+}
+}  // namespace
+
+size_t hkv_chain_scratch_words(size_t n) { return hkv::chain_scratch_words(n); }
+
+int hkv_debug_chain_stages(hkv_ctx* ctx, int dev, uint32_t stages) {
+  if (!dev_ok(ctx, dev)) return HKV_E_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ctx->devs[(size_t)dev].chain_stages = stages & hkv::CHAIN_STAGE_ALL;
+  return HKV_OK;
+}
+
+int hkv_chain_context_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, size_t n, const uint8_t* d_hashes,
+                             const hkv_chain_ctx* chain, const uint32_t* d_cp_heights, const uint8_t* d_cp_hashes,
+                             size_t n_cp, uint32_t* d_mtp, uint32_t* d_bits, uint8_t* d_work, uint8_t* d_status,
+                             uint32_t* d_scratch, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || n > 0xFFFFFF00ull) return HKV_E_ARG;
+  hkv::ChainStage s{};
+  HKV_RC(chain_ctx_of(chain, n, s.ctx));
+  if (n == 0) return HKV_OK;
+  if (!chain_ptrs_ok(d_headers, d_hashes, d_cp_heights, d_cp_hashes, n_cp, d_mtp, d_bits, d_work, d_status, d_scratch))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  s.headers = d_headers, s.n = (uint32_t)n, s.hashes = d_hashes, s.cp_heights = d_cp_heights,
+  s.cp_hashes = d_cp_hashes, s.n_cp = (uint32_t)n_cp, s.mtp = d_mtp, s.bits = d_bits,
+  s.work = reinterpret_cast<uint32_t*>(d_work), s.status = d_status, s.scratch = d_scratch;
+  // (the stage hook is read without a lock, as hkv_block_spends_device reads its own)
+  HKV_TRY(hkv::launch_chain_context(s, ctx->devs[(size_t)dev].chain_stages, c.st), "chain context launch");
+  return HKV_OK;
+}
+
+int hkv_connect_headers_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, size_t n, const uint8_t* d_pow_limit,
+                               const uint8_t* d_prev_hash, const hkv_chain_ctx* chain, const uint32_t* d_cp_heights,
+                               const uint8_t* d_cp_hashes, size_t n_cp, uint8_t* d_hashes, uint8_t* d_hdr_status,
+                               uint32_t* d_mtp, uint32_t* d_bits, uint8_t* d_work, uint8_t* d_status,
+                               uint32_t* d_scratch, uint32_t* d_first_bad, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || n > 0xFFFFFF00ull) return HKV_E_ARG;
+  hkv::ChainStage s{};
+  HKV_RC(chain_ctx_of(chain, n, s.ctx));
+  if (n == 0) return HKV_OK;
+  if (!d_pow_limit || !d_hashes || !d_hdr_status || !d_first_bad || !aligned(d_pow_limit, 4) ||
+      !aligned(d_prev_hash, 4) || !aligned(d_first_bad, 4) ||
+      !chain_ptrs_ok(d_headers, d_hashes, d_cp_heights, d_cp_hashes, n_cp, d_mtp, d_bits, d_work, d_status, d_scratch))
+    return HKV_E_ARG;
+  Call c(ctx, dev, hip_stream, Lock::None);
+  HKV_RC(c.rc);
+  HKV_TRY(hkv::launch_headers(d_headers, (uint32_t)n, d_pow_limit, d_prev_hash, d_hashes, d_hdr_status, c.st),
+          "headers launch");
+  s.headers = d_headers, s.n = (uint32_t)n, s.hashes = d_hashes, s.cp_heights = d_cp_heights,
+  s.cp_hashes = d_cp_hashes, s.n_cp = (uint32_t)n_cp, s.mtp = d_mtp, s.bits = d_bits,
+  s.work = reinterpret_cast<uint32_t*>(d_work), s.status = d_status, s.scratch = d_scratch,
+  s.hdr_status = d_hdr_status, s.first_bad = d_first_bad;
+  HKV_TRY(hkv::launch_chain_context(s, ctx->devs[(size_t)dev].chain_stages, c.st), "chain context launch");
+  return HKV_OK;
+}
+
+int hkv_connect_headers(hkv_ctx* ctx, const uint8_t* headers, size_t n, const uint8_t* prev_hash,
+                        const hkv_chain_ctx* chain, const uint32_t* cp_heights, const uint8_t* cp_hashes, size_t n_cp,
+                        uint8_t* hashes_out, uint8_t* hdr_status, uint32_t* mtp_out, uint32_t* bits_out,
+                        uint8_t* work_out, uint8_t* chain_status, size_t* n_ok) {
+  if (!ctx || ctx->devs.empty() || n > 0xFFFFFF00ull || n_cp > 0xFFFFFFFFull || !n_ok) return HKV_E_ARG;
+  hkv::ChainStage s{};
+  HKV_RC(chain_ctx_of(chain, n, s.ctx));
+  if (n_cp && (!cp_heights || !cp_hashes)) return HKV_E_ARG;
+  for (size_t k = 1; k < n_cp; ++k)
+    if (cp_heights[k] <= cp_heights[k - 1]) return HKV_E_ARG;
+  *n_ok = 0;
+  if (n == 0) return HKV_OK;
+  if (!headers || !hashes_out || !hdr_status) return HKV_E_ARG;
+  Call c(ctx, 0, Lock::Mu);
+  hkv::Layout l;  // one staging buffer: inputs, then outputs, then the stage's scratch
+  const size_t o_lim = l.add(32, 4), o_prev = l.add(32, 4), o_h = l.add(n * 80, 4), o_cph = l.add(n_cp * 4, 4),
+               o_cpx = l.add(n_cp * 32, 4), o_hash = l.add(n * 32, 16), o_st = l.add(n, 1), o_mtp = l.add(n * 4, 4),
+               o_bits = l.add(n * 4, 4), o_work = l.add(n * 32, 16), o_cst = l.add(n, 1), o_fb = l.add(4, 4),
+               o_scr = l.add(hkv::chain_scratch_words(n) * 4, 4);
+  HKV_RC(c.acquire());
+  HKV_RC(c.d.stage_headers.reserve(l.total, "hipMalloc(header batch)"));
+  uint8_t* b = c.d.stage_headers;
+  HKV_TRY(hipMemcpyAsync(b + o_lim, chain->pow_limit, 32, hipMemcpyHostToDevice, c.st), "H2D pow limit");
+  if (prev_hash) HKV_TRY(hipMemcpyAsync(b + o_prev, prev_hash, 32, hipMemcpyHostToDevice, c.st), "H2D prev");
+  HKV_TRY(hipMemcpyAsync(b + o_h, headers, n * 80, hipMemcpyHostToDevice, c.st), "H2D headers");
+  if (n_cp) {
+    HKV_TRY(hipMemcpyAsync(b + o_cph, cp_heights, n_cp * 4, hipMemcpyHostToDevice, c.st), "H2D checkpoint heights");
+    HKV_TRY(hipMemcpyAsync(b + o_cpx, cp_hashes, n_cp * 32, hipMemcpyHostToDevice, c.st), "H2D checkpoint hashes");
+  }
+  HKV_TRY(hkv::launch_headers(b + o_h, (uint32_t)n, b + o_lim, prev_hash ? b + o_prev : nullptr, b + o_hash, b + o_st,
+                              c.st),
+          "headers launch");
+  s.headers = b + o_h, s.n = (uint32_t)n, s.hashes = b + o_hash,
+  s.cp_heights = reinterpret_cast<const uint32_t*>(b + o_cph), s.cp_hashes = b + o_cpx, s.n_cp = (uint32_t)n_cp,
+  s.mtp = reinterpret_cast<uint32_t*>(b + o_mtp), s.bits = reinterpret_cast<uint32_t*>(b + o_bits),
+  s.work = reinterpret_cast<uint32_t*>(b + o_work), s.status = b + o_cst,
+  s.scratch = reinterpret_cast<uint32_t*>(b + o_scr), s.hdr_status = b + o_st,
+  s.first_bad = reinterpret_cast<uint32_t*>(b + o_fb);
+  HKV_TRY(hkv::launch_chain_context(s, hkv::CHAIN_STAGE_ALL, c.st), "chain context launch");
+  uint32_t first_bad = 0;
+  HKV_TRY(hipMemcpyAsync(hashes_out, b + o_hash, n * 32, hipMemcpyDeviceToHost, c.st), "D2H header hashes");
+  HKV_TRY(hipMemcpyAsync(hdr_status, b + o_st, n, hipMemcpyDeviceToHost, c.st), "D2H header status");
+  if (mtp_out) HKV_TRY(hipMemcpyAsync(mtp_out, b + o_mtp, n * 4, hipMemcpyDeviceToHost, c.st), "D2H mtp");
+  if (bits_out) HKV_TRY(hipMemcpyAsync(bits_out, b + o_bits, n * 4, hipMemcpyDeviceToHost, c.st), "D2H want bits");
+  if (work_out) HKV_TRY(hipMemcpyAsync(work_out, b + o_work, n * 32, hipMemcpyDeviceToHost, c.st), "D2H chain work");
+  if (chain_status) HKV_TRY(hipMemcpyAsync(chain_status, b + o_cst, n, hipMemcpyDeviceToHost, c.st), "D2H chain status");
+  HKV_TRY(hipMemcpyAsync(&first_bad, b + o_fb, 4, hipMemcpyDeviceToHost, c.st), "D2H first bad");
+  HKV_TRY(hipStreamSynchronize(c.st), "connect headers sync");
+  *n_ok = first_bad;
+  return c.done();
 }
 
 }  // extern "C"

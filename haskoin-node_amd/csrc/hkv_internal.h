@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/hkv.h"
+#include "hkv_chainctx.h"
 #include "hkv_launch_plan.h"
 
 #define HKV_MODE_LIBSECP 0u
@@ -300,6 +301,28 @@ constexpr uint32_t SPEND_STAGE_WALK = 1u, SPEND_STAGE_TABLE = 2u, SPEND_STAGE_SP
 // the walk, the table (a memset on st, then one insert per input), the
 // spender lookup and the fold; with n_inputs == 0 only the two per-tx launches
 hipError_t launch_block_spends(const SpendStage& s, uint32_t stages, hipStream_t st);
+// hkv_chainctx.hip: the chain-context stage behind the header checks
+// (hkv_chainctx.h states the rule and sizes the scratch).
+struct ChainStage {
+  const uint8_t* headers;
+  uint32_t n;
+  ChainCtx ctx;
+  const uint8_t* hashes;  // read at checkpoint heights only: may be null when n_cp == 0
+  const uint32_t* cp_heights;
+  const uint8_t* cp_hashes;
+  uint32_t n_cp;
+  uint32_t* mtp;
+  uint32_t* bits;
+  uint32_t* work;
+  uint8_t* status;
+  uint32_t* scratch;          // chain_scratch_words(n) words
+  const uint8_t* hdr_status;  // with first_bad: the hkv_check_headers status bytes
+  uint32_t* first_bad;        // or null: no reduction
+};
+// the launches, in stream order (hkv_debug_chain_stages: a bench leaves some out)
+constexpr uint32_t CHAIN_STAGE_FACTS = 1u, CHAIN_STAGE_SCAN = 2u, CHAIN_STAGE_VERDICT = 4u, CHAIN_STAGE_FIRST_BAD = 8u,
+                   CHAIN_STAGE_ALL = 15u;
+hipError_t launch_chain_context(const ChainStage& s, uint32_t stages, hipStream_t st);
 // hkv_headers.hip
 hipError_t launch_headers(const uint8_t* hdrs, uint32_t n, const uint8_t* pow_limit, const uint8_t* prev0,
                           uint8_t* hashes, uint8_t* status, hipStream_t st);

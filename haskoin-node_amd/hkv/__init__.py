@@ -21,6 +21,11 @@ from .blocktx import (HKV_SRC_LIST, HKV_SRC_NONE, block_layout, block_tx_jobs_de
 from .spends import (HKV_SPEND_BALANCED, HKV_SPEND_COINBASE, HKV_SPEND_FIRST, HKV_SPEND_IN_RANGE, HKV_SPEND_OK,
                      HKV_SPEND_OUT_RANGE, HKV_SPEND_RESOLVED, block_spends_device, check_block_txs,
                      debug_spend_stages, spend_table_slots, verify_block_txs_spends_host)
+from .chain import (HKV_CHAIN_MIN_DIFFICULTY, HKV_CHAIN_NO_RETARGET, HKV_CHN_ALL, HKV_CHN_BITS_OK,
+                    HKV_CHN_CHECKPOINT_OK, HKV_CHN_NOT_FUTURE, HKV_CHN_TIME_OK, HKV_CHN_VERSION_OK, ChainParams,
+                    ChainTip, ConnectResult, chain_context_device, chain_ctx, chain_scratch_words, connect_headers,
+                    connect_headers_device, debug_chain_stages)
+from .chain import PARAMS as CHAIN_PARAMS
 from .verify import (Verifier, VerifierConfig, verify_hash_sig_batch,
                      verify_raw_batch)
 from .actor import VerifyActor, VerifyActorConfig
@@ -41,5 +46,9 @@ __all__ = [
     "spend_table_slots", "block_spends_device", "verify_block_txs_spends_host", "check_block_txs",
     "debug_spend_stages", "HKV_SPEND_RESOLVED", "HKV_SPEND_FIRST", "HKV_SPEND_IN_RANGE", "HKV_SPEND_OUT_RANGE",
     "HKV_SPEND_BALANCED", "HKV_SPEND_COINBASE", "HKV_SPEND_OK",
+    "connect_headers", "connect_headers_device", "chain_context_device", "chain_scratch_words", "chain_ctx",
+    "debug_chain_stages", "ChainParams", "ChainTip", "ConnectResult", "CHAIN_PARAMS", "HKV_CHN_TIME_OK",
+    "HKV_CHN_NOT_FUTURE", "HKV_CHN_BITS_OK", "HKV_CHN_VERSION_OK", "HKV_CHN_CHECKPOINT_OK", "HKV_CHN_ALL",
+    "HKV_CHAIN_NO_RETARGET", "HKV_CHAIN_MIN_DIFFICULTY",
     "HKV_TXID_OK", "HKV_TXID_BAD_TX", "HKV_BLK_MERKLE_OK", "HKV_BLK_MUTATED", "HKV_BLK_BAD_TX", "HKV_BLK_EMPTY",
 ]

@@ -17,7 +17,8 @@ Batch equivalent (same per-element result):
         -> (hashes: list of 32-byte digests, status: uint8[n] of HKV_HDR_* flags)
 
 The chain-context checks of connectBlocks (median time past, future-time
-limit, nextWorkRequired, checkpoints, BIP34 height) stay on the host.
+limit, nextWorkRequired, validVersion, checkpoints, chain work) are the stage
+behind these: ``hkv.chain.connect_headers`` (csrc/hkv_chainctx.hip).
 """
 from __future__ import annotations
 

@@ -29,6 +29,9 @@ HKV_STATUS_INPUT_COUNT = 2
 HKV_SRC_NONE, HKV_SRC_LIST = 0xFFFFFFFF, 0xFFFFFFFE
 HKV_SPEND_RESOLVED, HKV_SPEND_FIRST, HKV_SPEND_IN_RANGE, HKV_SPEND_OUT_RANGE = 0x01, 0x02, 0x04, 0x08
 HKV_SPEND_BALANCED, HKV_SPEND_COINBASE, HKV_SPEND_OK = 0x10, 0x20, 0x1F
+HKV_CHN_TIME_OK, HKV_CHN_NOT_FUTURE, HKV_CHN_BITS_OK, HKV_CHN_VERSION_OK = 0x01, 0x02, 0x04, 0x08
+HKV_CHN_CHECKPOINT_OK, HKV_CHN_ALL = 0x10, 0x1F
+HKV_CHAIN_NO_RETARGET, HKV_CHAIN_MIN_DIFFICULTY = 1, 2
 _ERRS = {-1: "HKV_E_ARG", -2: "HKV_E_NODEV", -3: "HKV_E_OOM", -4: "HKV_E_HIP", -5: "HKV_E_INTERNAL"}
 
 _PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,7 +69,17 @@ class HkvInputJob(ctypes.Structure):
                 ("value", c_uint64)]
 
 
-assert ctypes.sizeof(HkvSighashJob) == 32 and ctypes.sizeof(HkvInputJob) == 24
+class HkvChainCtx(ctypes.Structure):
+    """struct hkv_chain_ctx (include/hkv.h)."""
+    _fields_ = [("height0", c_uint32), ("n_prev_times", c_uint32), ("prev_times", c_uint32 * 11),
+                ("parent_bits", c_uint32), ("period_first_time", c_uint32), ("period_real_bits", c_uint32),
+                ("parent_work", c_uint8 * 32), ("now", c_uint64), ("pow_limit", c_uint8 * 32),
+                ("interval", c_uint32), ("target_timespan", c_uint32), ("min_diff_spacing", c_uint32),
+                ("bip34_height", c_uint32), ("bip66_height", c_uint32), ("bip65_height", c_uint32),
+                ("flags", c_uint32)]
+
+
+assert ctypes.sizeof(HkvSighashJob) == 32 and ctypes.sizeof(HkvInputJob) == 24 and ctypes.sizeof(HkvChainCtx) == 168
 
 # name -> (restype, argtypes)
 EXPORTS = {
@@ -148,6 +161,17 @@ EXPORTS = {
     "hkv_check_headers": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hkv_check_headers_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "hkv_chain_scratch_words": (c_size_t, [c_size_t]),
+    "hkv_chain_context_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, POINTER(HkvChainCtx), c_void_p,
+                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "hkv_connect_headers_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                           POINTER(HkvChainCtx), c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hkv_connect_headers": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, POINTER(HkvChainCtx), c_void_p, c_void_p,
+                                    c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    POINTER(c_size_t)]),
+    "hkv_debug_chain_stages": (c_int, [c_void_p, c_int, c_uint32]),
     "hkv_gen_keys_device": (c_int, [c_void_p, c_int, c_uint64, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hkv_gen_sign_device": (c_int, [c_void_p, c_int, c_uint64, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p, c_void_p]),

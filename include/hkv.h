@@ -60,6 +60,10 @@
  *       replaces the per-header part of haskoin-core `connectBlocks` reached
  *       from importHeaders (/root/reference/src/Haskoin/Node/Chain.hs:500-520):
  *       headerHash, isValidPOW (decodeCompact) and the prev-hash link.
+ *   hkv_connect_headers / hkv_connect_headers_device / hkv_chain_context_device
+ *       replaces the rest of that `connectBlocks` call: median time past, the
+ *       future-time limit, nextWorkRequired, validVersion, checkpoints and the
+ *       chain work, and the count of leading headers that connect.
  *   hkv_tx_ids / hkv_tx_ids_device
  *       replaces N calls of haskoin-core `txHash :: Tx -> TxHash`
  *       (SHA-256d of the tx re-serialised without witness data).
@@ -446,7 +450,8 @@ int hkv_verify_std_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_of
  * headerPOW h <= target, with (target, overflow) = decodeCompact h.bits;
  * plus the batch linkage connectBlocks relies on (prev field of header i
  * == headerHash of header i-1). The chain-context checks (median time past,
- * retarget / nextWorkRequired, checkpoints, BIP34) stay on the host.
+ * retarget / nextWorkRequired, checkpoints, validVersion, chain work) are the
+ * stage below (hkv_chain_context_device, hkv_connect_headers*).
  * ------------------------------------------------------------------------ */
 #define HKV_HDR_POW_OK 0x01u           /* isValidPOW                               */
 #define HKV_HDR_LINK_OK 0x02u          /* prev == hash of the previous header      */
@@ -467,6 +472,130 @@ int hkv_check_headers(hkv_ctx* ctx, const uint8_t* headers, size_t n, const uint
  * not synchronised. */
 int hkv_check_headers_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, size_t n, const uint8_t* d_pow_limit,
                              const uint8_t* d_prev_hash, uint8_t* d_hashes, uint8_t* d_status, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
+ * Header chain context: the rest of connectBlocks [dep] behind the per-header
+ * checks above, so that a `headers` message goes in and connectBlocks' answer
+ * comes out (importHeaders, reference src/Haskoin/Node/Chain.hs:500-520):
+ * how many leading headers connect, and each header's height-dependent facts.
+ * Every check is a function of a header's actual ancestors (the batch's earlier
+ * headers, then the context), never of an earlier verdict: a header's flags
+ * presume that its ancestors are as given.
+ *
+ * Header i of the batch has height H = height0 + i. Its parent P is header
+ * i - 1, or the context's tip when i = 0. With limit_bits =
+ * encodeCompact(pow_limit):
+ *   mtp[i]    element c / 2 of the ascending sort of the c = min(11, i +
+ *             n_prev_times) timestamps before header i (the batch's, then the
+ *             context's; unsigned compare).
+ *   want[i]   Bitcoin's GetNextWorkRequired.
+ *             H mod interval != 0: bits(P); with HKV_CHAIN_MIN_DIFFICULTY,
+ *             limit_bits when time[i] > time(P) + min_diff_spacing (64 bits),
+ *             else real(P), where real(b) = bits(b) if height(b) mod interval
+ *             = 0 or bits(b) != limit_bits, else real(parent of b); real(tip)
+ *             is period_real_bits.
+ *             H mod interval == 0: bits(P) with HKV_CHAIN_NO_RETARGET; else
+ *             encodeCompact(min(pow_limit, target(P) * span /
+ *             target_timespan)) in exact integers, span = time(P) - time(F)
+ *             (signed, 64 bits) clamped to [target_timespan / 4,
+ *             4 * target_timespan], F the block at height H - interval
+ *             (header i - interval, or period_first_time when i < interval),
+ *             target(P) decodeCompact's magnitude. A parent compact that
+ *             overflows gives want = 0 and clears BITS_OK.
+ *   work[i]   parent_work + the sum over j <= i of headerWork(j), mod 2^256,
+ *             32 little-endian bytes; headerWork = floor(2^256 / (target + 1)),
+ *             and 0 for a compact that is negative, overflowing or zero.
+ *   HKV_CHN_TIME_OK        time[i] > mtp[i]
+ *   HKV_CHN_NOT_FUTURE     time[i] <= now + 7200 (64 bits)
+ *   HKV_CHN_BITS_OK        bits[i] == want[i]
+ *   HKV_CHN_VERSION_OK     validVersion: the version read as a signed number;
+ *                          below 2 needs H < bip34_height, below 3 needs
+ *                          H < bip66_height, below 4 needs H < bip65_height
+ *   HKV_CHN_CHECKPOINT_OK  no checkpoint has height H, or its hash equals
+ *                          headerHash(i) as hkv_check_headers* wrote it (the
+ *                          BIP34 block is one more checkpoint of the caller's)
+ *   HKV_CHN_ALL            the five together
+ * BCH's EDA / DAA / ASERT difficulty rules are not covered, nor afterLastCP
+ * (it depends on the store's best block).
+ * ------------------------------------------------------------------------ */
+#define HKV_CHN_TIME_OK 0x01u
+#define HKV_CHN_NOT_FUTURE 0x02u
+#define HKV_CHN_BITS_OK 0x04u
+#define HKV_CHN_VERSION_OK 0x08u
+#define HKV_CHN_CHECKPOINT_OK 0x10u
+#define HKV_CHN_ALL 0x1Fu
+#define HKV_CHAIN_NO_RETARGET 1u    /* regtest: a boundary keeps bits(P)             */
+#define HKV_CHAIN_MIN_DIFFICULTY 2u /* testnet: the minimum-difficulty rule and walk */
+/* What header 0 stands on, and the network's constants. Read on the host when a
+ * call is enqueued and passed to the kernels by value. */
+typedef struct hkv_chain_ctx {
+  uint32_t height0;            /* header 0's height, >= 1                                        */
+  uint32_t n_prev_times;       /* 1..11                                                          */
+  uint32_t prev_times[11];     /* header 0's nearest ancestors' times, oldest first, the parent's last */
+  uint32_t parent_bits;
+  uint32_t period_first_time;  /* time of the block at (height0-1) - ((height0-1) mod interval)  */
+  uint32_t period_real_bits;   /* real(tip), see want[i]                                         */
+  uint8_t parent_work[32];     /* the tip's chain work, little-endian                            */
+  uint64_t now;                /* seconds, below 2^63                                            */
+  uint8_t pow_limit[32];       /* little-endian                                                  */
+  uint32_t interval;           /* 2016; not 0                                                    */
+  uint32_t target_timespan;    /* 1,209,600; within [4, 2^30)                                    */
+  uint32_t min_diff_spacing;   /* 1,200                                                          */
+  uint32_t bip34_height, bip66_height, bip65_height;
+  uint32_t flags;              /* HKV_CHAIN_*                                                    */
+} hkv_chain_ctx;
+/* The scratch of the stage for n headers, in 32-bit words (3 per header and 20
+ * per tile of 256 headers). */
+size_t hkv_chain_scratch_words(size_t n);
+/* The stage on device (replaces the caller's walk of connectBlocks' context
+ * checks: medianTime, nextWorkRequired, validVersion, the checkpoint test and the
+ * chain work of haskoin-core Haskoin.Block.Headers [dep]).
+ * Stateless and without a lock as hkv_block_spends_device; three launches on
+ * hip_stream, enqueued and not synchronised. In: d_headers (n * 80 bytes,
+ * 4-aligned), d_hashes (n * 32 bytes as hkv_check_headers_device wrote them on
+ * the same stream, 16-aligned; NULL is allowed when n_cp == 0), the
+ * checkpoints d_cp_heights (n_cp words, ascending: the caller vouches for the
+ * order here, the host form checks it) and d_cp_hashes (n_cp * 32 bytes, digest
+ * order, 4-aligned). Out: d_mtp and d_bits (= want; n words each), d_work
+ * (n * 32 bytes, 16-aligned), d_status (n bytes of HKV_CHN_*). d_scratch:
+ * hkv_chain_scratch_words(n) words. HKV_E_ARG for height0 == 0, height0 + n
+ * above 2^32 - 1, n_prev_times outside 1..11, interval == 0, target_timespan
+ * outside [4, 2^30), checkpoints without d_hashes, a NULL or misaligned
+ * pointer. HKV_OK for n == 0, with nothing launched. */
+int hkv_chain_context_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, size_t n, const uint8_t* d_hashes,
+                             const hkv_chain_ctx* chain, const uint32_t* d_cp_heights, const uint8_t* d_cp_hashes,
+                             size_t n_cp, uint32_t* d_mtp, uint32_t* d_bits, uint8_t* d_work, uint8_t* d_status,
+                             uint32_t* d_scratch, void* hip_stream);
+/* connectBlocks on device (replaces the connectBlocks call of importHeaders):
+ * hkv_check_headers_device (d_pow_limit, d_prev_hash, d_hashes, d_hdr_status
+ * as there; d_pow_limit holds chain->pow_limit), then the stage, then a
+ * reduction into *d_first_bad: the smallest i whose chain flags are not
+ * HKV_CHN_ALL or whose header status lacks HKV_HDR_POW_OK or HKV_HDR_LINK_OK,
+ * n when there is none: the number of headers connectBlocks would connect.
+ * Five launches on hip_stream, enqueued and not synchronised. d_hashes is
+ * always needed here. With n == 0 nothing is launched and *d_first_bad is
+ * not written. */
+int hkv_connect_headers_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, size_t n, const uint8_t* d_pow_limit,
+                               const uint8_t* d_prev_hash, const hkv_chain_ctx* chain, const uint32_t* d_cp_heights,
+                               const uint8_t* d_cp_hashes, size_t n_cp, uint8_t* d_hashes, uint8_t* d_hdr_status,
+                               uint32_t* d_mtp, uint32_t* d_bits, uint8_t* d_work, uint8_t* d_status,
+                               uint32_t* d_scratch, uint32_t* d_first_bad, void* hip_stream);
+/* Host-memory form of the same (replaces connectBlocks net ... headers): every
+ * pointer in host memory, first device, blocking. prev_hash as
+ * hkv_check_headers. Any of mtp_out, bits_out, work_out, chain_status may be
+ * NULL; hashes_out, hdr_status and n_ok may not. *n_ok = first_bad. Also
+ * HKV_E_ARG for checkpoint heights that are not strictly ascending. n == 0
+ * succeeds with *n_ok = 0. */
+int hkv_connect_headers(hkv_ctx* ctx, const uint8_t* headers, size_t n, const uint8_t* prev_hash,
+                        const hkv_chain_ctx* chain, const uint32_t* cp_heights, const uint8_t* cp_hashes, size_t n_cp,
+                        uint8_t* hashes_out, uint8_t* hdr_status, uint32_t* mtp_out, uint32_t* bits_out,
+                        uint8_t* work_out, uint8_t* chain_status, size_t* n_ok);
+/* Measurement hook (no reference counterpart): device dev's later chain-context
+ * calls run only the launches named in stages (bit 0 the facts, bit 1 the tile
+ * scan, bit 2 the verdicts, bit 3 the first_bad reduction; default 15), so a
+ * bench can time each on scratch a full call filled before. Results of a
+ * partial call mean nothing. */
+int hkv_debug_chain_stages(hkv_ctx* ctx, int dev, uint32_t stages);
 
 /* ---------------------------------------------------------------------------
  * Block merkle roots: haskoin-core buildMerkleRoot [dep, haskoin-core-1.1.0
