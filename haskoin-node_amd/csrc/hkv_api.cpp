@@ -198,8 +198,10 @@ struct hkv_ctx {
   // mu: every entry point's host-side state (DevCtx fields, allocations,
   // enqueue order). tx_mu[k]: the tx-index rows, the multisig scratch and
   // the tx staging of device k — held by the sighash / std-input entry
-  // points for their whole call, taken BEFORE mu. No entry point waits on
-  // the device while it holds either (the device forms only enqueue).
+  // points for their whole call, taken BEFORE mu. The device forms only
+  // enqueue while they hold them; the blocking host forms hold theirs across
+  // their waits for the device (hipStreamSynchronize inside the Call scope, and
+  // verify_from_host's joins), so a second caller waits for that work too.
   std::mutex mu;
   std::vector<std::unique_ptr<std::mutex>> tx_mu;
   // host-batch failover (verify_from_host): devices still in use, and how
@@ -762,7 +764,7 @@ int enqueue_verify_std_inputs(DevCtx& d, const hkv_txs* dt, const hkv_input_job*
 }
 
 // copy a host tx batch (+ jobs) into the device's staging buffers
-int stage_txs(DevCtx& d, const hkv_txs* h, const void* jobs, size_t job_bytes, hkv_txs* dt, void** djobs) {
+int stage_txs(DevCtx& d, const hkv_txs* h, const void* jobs, size_t job_bytes, hkv_txs* dt, void** djobs = nullptr) {
   const size_t nbytes = h->n_tx ? h->offsets[h->n_tx] : 0;
   const size_t noff = (size_t)h->n_tx + 1;
   HKV_RC(d.stage_tx_bytes.reserve(nbytes, "hipMalloc(tx bytes)"));
@@ -781,8 +783,15 @@ int stage_txs(DevCtx& d, const hkv_txs* h, const void* jobs, size_t job_bytes, h
   dt->n_tx = h->n_tx;
   dt->scripts = d.stage_scripts;
   dt->scripts_len = h->scripts_len;
-  *djobs = d.stage_jobs.get();
+  if (djobs) *djobs = d.stage_jobs.get();
   return HKV_OK;
+}
+// the same for an entry point that reads no script and has no jobs: the pool
+// is not staged
+int stage_txs_no_pool(DevCtx& d, const hkv_txs* h, hkv_txs* dt) {
+  hkv_txs in = *h;
+  in.scripts = nullptr, in.scripts_len = 0;
+  return stage_txs(d, &in, nullptr, 0, dt);
 }
 
 // whether dev names a device of ctx (checked before any lock is taken)
@@ -831,6 +840,21 @@ class Call {
   std::unique_lock<std::mutex> tx_, mu_;
   bool held_ = false;
 };
+
+// The end of a blocking host form that ran the standard-input verify: read
+// the call's status word behind everything the call enqueued, wait (sync: the
+// wait's name in an error text), and end the call — with HKV_E_INTERNAL when
+// a multisig tail queue wait gave up (its verdicts are incomplete).
+int finish_status_call(Call& c, const uint32_t* status, const char* sync) {
+  uint32_t fault = 0;
+  HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
+  HKV_TRY(hipStreamSynchronize(c.st), sync);
+  if (fault & HKV_STATUS_TAIL_FAULT) {
+    g_last_hip = "multisig tail: work-queue wait timed out";
+    return c.done(HKV_E_INTERNAL);
+  }
+  return c.done();
+}
 
 }  // namespace
 
@@ -1391,14 +1415,7 @@ int hkv_verify_std_inputs(hkv_ctx* ctx, const hkv_txs* txs, const hkv_input_job*
   HKV_RC(enqueue_verify_std_inputs(d, &dt, static_cast<const hkv_input_job*>(djobs), n, forkid, d.recs,
                                    d.host_std_bits, c.st));
   HKV_TRY(hipMemcpyAsync(verdict_bits, d.host_std_bits, (n + 31) / 32 * 4, hipMemcpyDeviceToHost, c.st), "D2H bits");
-  uint32_t fault = 0;
-  HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
-  HKV_TRY(hipStreamSynchronize(c.st), "std inputs sync");
-  if (fault & HKV_STATUS_TAIL_FAULT) {  // a multisig tail queue wait gave up (its verdicts are incomplete)
-    g_last_hip = "multisig tail: work-queue wait timed out";
-    return c.done(HKV_E_INTERNAL);
-  }
-  return c.done();
+  return finish_status_call(c, status, "std inputs sync");
 }
 
 int hkv_gen_keys_device(hkv_ctx* ctx, int dev, uint64_t seed, size_t n, uint8_t* d_priv, uint8_t* d_pub,
@@ -1485,9 +1502,7 @@ int hkv_merkle_roots(hkv_ctx* ctx, const uint8_t* txids, const uint32_t* offsets
   if (!ctx || ctx->devs.empty() || n_blocks > 0x7FFFFFFFull) return HKV_E_ARG;
   if (n_blocks == 0) return HKV_OK;
   if (!offsets || !roots_out || !mutated) return HKV_E_ARG;
-  if (offsets[0] != 0) return HKV_E_ARG;
-  for (size_t b = 0; b < n_blocks; ++b)
-    if (offsets[b + 1] < offsets[b]) return HKV_E_ARG;
+  if (offsets[0] != 0 || !hkv::offsets_nondecreasing(offsets, n_blocks)) return HKV_E_ARG;
   const size_t leaves = offsets[n_blocks];
   if (leaves && !txids) return HKV_E_ARG;
   Call c(ctx, 0, Lock::Mu);
@@ -1514,11 +1529,7 @@ int hkv_merkle_roots(hkv_ctx* ctx, const uint8_t* txids, const uint32_t* offsets
 
 // a host batch's offsets must not decrease: tx t is then inside the
 // offsets[n_tx] bytes that are staged, whatever it holds
-static bool tx_offsets_sorted(const hkv_txs* t) {
-  for (uint32_t k = 0; k < t->n_tx; ++k)
-    if (t->offsets[k + 1] < t->offsets[k]) return false;
-  return true;
-}
+static bool tx_offsets_sorted(const hkv_txs* t) { return hkv::offsets_nondecreasing(t->offsets, t->n_tx); }
 
 int hkv_tx_ids_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, uint8_t* d_txids, uint8_t* d_status,
                       void* hip_stream) {
@@ -1538,14 +1549,11 @@ int hkv_tx_ids(hkv_ctx* ctx, const hkv_txs* txs, uint8_t* txids_out, uint8_t* st
   if (!txids_out || !tx_offsets_sorted(txs)) return HKV_E_ARG;
   Call c(ctx, 0, Lock::Tx);  // (the tx staging of device 0)
   DevCtx& d = c.d;
-  hkv_txs in = *txs, dt;  // the scripts pool is not read: not staged
-  in.scripts = nullptr;
-  in.scripts_len = 0;
-  void* unused = nullptr;
+  hkv_txs dt;
   hkv::Layout l;  // txids | status bytes
   const size_t o_id = l.add(n * 32, 16), o_status = l.add(n, 1);
   HKV_RC(c.acquire());
-  HKV_RC(stage_txs(d, &in, nullptr, 0, &dt, &unused));
+  HKV_RC(stage_txs_no_pool(d, txs, &dt));
   HKV_RC(d.stage_out.reserve(l.total, "hipMalloc(txid out)"));
   uint8_t *dout = d.stage_out + o_id, *dstat = d.stage_out + o_status;
   HKV_TRY(hkv::launch_txids(dt.bytes, dt.offsets, dt.n_tx, dout, dstat, c.st), "txid launch");
@@ -1580,17 +1588,14 @@ int hkv_check_blocks(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* block_off
                      const uint8_t* headers, uint8_t* txids_out, uint8_t* roots_out, uint8_t* status) {
   if (!ctx || ctx->devs.empty() || !txs_ok(txs) || n_blocks > 0x7FFFFFFFull) return HKV_E_ARG;
   if (n_blocks == 0) return HKV_OK;
-  if (!block_offsets || !headers || !status || block_offsets[0] != 0) return HKV_E_ARG;
-  for (size_t b = 0; b < n_blocks; ++b)
-    if (block_offsets[b + 1] < block_offsets[b]) return HKV_E_ARG;
+  if (!block_offsets || !headers || !status || block_offsets[0] != 0 ||
+      !hkv::offsets_nondecreasing(block_offsets, n_blocks))
+    return HKV_E_ARG;
   const size_t n = txs->n_tx;
   if (block_offsets[n_blocks] > n || !tx_offsets_sorted(txs)) return HKV_E_ARG;
   Call c(ctx, 0, Lock::Tx);  // (the tx staging of device 0)
   DevCtx& d = c.d;
-  hkv_txs in = *txs, dt;  // the scripts pool is not read: not staged
-  in.scripts = nullptr;
-  in.scripts_len = 0;
-  void* unused = nullptr;
+  hkv_txs dt;
   const size_t off_bytes = (n_blocks + 1) * 4;
   // one staging buffer beside the tx staging: txids | scratch | roots | headers | offsets | mutated | status
   hkv::Layout l;
@@ -1598,7 +1603,7 @@ int hkv_check_blocks(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* block_off
                o_h = l.add(n_blocks * 80, 4), o_off = l.add(off_bytes, 4), o_m = l.add(n_blocks, 1),
                o_st = l.add(n_blocks, 1);
   HKV_RC(c.acquire());
-  HKV_RC(stage_txs(d, &in, nullptr, 0, &dt, &unused));
+  HKV_RC(stage_txs_no_pool(d, txs, &dt));
   HKV_RC(d.stage_blocks.reserve(l.total, "hipMalloc(block batch)"));
   uint8_t* b = d.stage_blocks;
   uint8_t *dl = b + o_l, *dsc = b + o_sc, *dr = b + o_r, *dh = b + o_h, *doff = b + o_off, *dm = b + o_m,
@@ -1659,112 +1664,7 @@ int hkv_tx_verdicts_device(hkv_ctx* ctx, int dev, const uint32_t* d_input_first,
   return HKV_OK;
 }
 
-// the three stages of batch verifyStdTx on c's stream (the caller holds the
-// Tx lock and has acquired the scratch with status as the call's status word)
-static int enqueue_verify_std_txs(Call& c, const hkv_txs* dt, const hkv::StdPrevouts& p, int32_t forkid,
-                                  size_t n_inputs, uint32_t* first, hkv_input_job* jobs, void* recs,
-                                  uint32_t* input_bits, uint32_t* tx_bits, uint32_t* status, bool counted) {
-  if (!counted)
-    HKV_TRY(hkv::launch_stdtx_counts(dt->bytes, dt->offsets, dt->n_tx, (uint32_t)n_inputs, first, status, c.st),
-            "input count launch");
-  HKV_TRY(hkv::launch_stdtx_jobs(dt->bytes, dt->offsets, dt->n_tx, first, p, (uint32_t)n_inputs, jobs, c.st),
-          "job builder launch");
-  if (n_inputs) HKV_RC(enqueue_verify_std_inputs(c.d, dt, jobs, n_inputs, forkid, recs, input_bits, c.st));
-  HKV_TRY(hkv::launch_tx_verdicts(first, dt->n_tx, input_bits, status, tx_bits, c.st), "tx verdict launch");
-  return HKV_OK;
-}
-
-int hkv_verify_std_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
-                              const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
-                              const uint64_t* d_prev_values, int32_t forkid, size_t n_inputs,
-                              uint32_t* d_input_first, hkv_input_job* d_jobs, void* d_records,
-                              uint32_t* d_input_bits, uint32_t* d_tx_bits, uint32_t* d_status, void* hip_stream) {
-  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
-  if (d_txs->n_tx == 0) return HKV_OK;
-  if (!prevouts_ok(d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values) || !d_input_first ||
-      !d_tx_bits || !d_status || (n_inputs && (!d_jobs || !d_records || !d_input_bits)) ||
-      !aligned(d_input_first, 4) || !aligned(d_status, 4) || !aligned(d_jobs, 8) || !aligned(d_input_bits, 4) ||
-      !aligned(d_tx_bits, 4) || !aligned(d_txs->offsets, 4))
-    return HKV_E_ARG;
-  Call c(ctx, dev, hip_stream, Lock::Tx);
-  int rc = c.acquire(d_status);
-  if (!rc)
-    rc = enqueue_verify_std_txs(c, d_txs, hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values},
-                                forkid, n_inputs, d_input_first, d_jobs, d_records, d_input_bits, d_tx_bits, d_status,
-                                false);
-  return c.done(rc);
-}
-
-int hkv_verify_std_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
-                       const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
-                       int32_t forkid, uint32_t* tx_verdict_bits) {
-  if (!ctx || ctx->devs.empty() || !txs_ok(txs)) return HKV_E_ARG;
-  const size_t n_tx = txs->n_tx;
-  if (n_tx == 0) return HKV_OK;
-  if (!prev_offsets || !tx_verdict_bits || !tx_offsets_sorted(txs)) return HKV_E_ARG;
-  for (size_t t = 0; t < n_tx; ++t)
-    if (prev_offsets[t + 1] < prev_offsets[t]) return HKV_E_ARG;
-  const size_t e0 = prev_offsets[0], n_ent = prev_offsets[n_tx] - e0;
-  if (n_ent && (!prev_outpoints || !prev_scripts || !prev_values)) return HKV_E_ARG;
-  Call c(ctx, 0, Lock::Tx);
-  DevCtx& d = c.d;
-  hkv_txs dt;
-  void* unused = nullptr;
-  uint32_t* status = reinterpret_cast<uint32_t*>(d.ms_bar + MS_HOST_STATUS);
-  // one staging buffer: values | entry offsets | script references | outpoints.
-  // Only the entries the offsets name are staged, so the staged offsets are
-  // rebased by the first one on the host.
-  hkv::Layout l;
-  const size_t o_val = l.add(n_ent * 8, 8), o_off = l.add((n_tx + 1) * 4, 4), o_scr = l.add(n_ent * 8, 4),
-               o_op = l.add(n_ent * 36, 4);
-  std::vector<uint32_t> rebased(n_tx + 1);
-  for (size_t t = 0; t <= n_tx; ++t) rebased[t] = (uint32_t)(prev_offsets[t] - e0);
-  HKV_RC(c.acquire(status));
-  HKV_RC(stage_txs(d, txs, nullptr, 0, &dt, &unused));
-  HKV_RC(d.stage_prev.reserve(l.total, "hipMalloc(prevouts)"));
-  HKV_RC(d.std_first.reserve(n_tx + 1, "hipMalloc(input offsets)"));
-  HKV_RC(d.host_tx_bits.reserve((n_tx + 63) / 64 * 2, "hipMalloc(tx verdict words)"));
-  uint8_t* b = d.stage_prev;
-  const hkv::StdPrevouts p{reinterpret_cast<const uint32_t*>(b + o_off), b + o_op,
-                           reinterpret_cast<const uint32_t*>(b + o_scr),
-                           reinterpret_cast<const uint64_t*>(b + o_val)};
-  HKV_TRY(hipMemcpyAsync(b + o_off, rebased.data(), (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D prevout offsets");
-  if (n_ent) {
-    HKV_TRY(hipMemcpyAsync(b + o_op, prev_outpoints + e0 * 36, n_ent * 36, hipMemcpyHostToDevice, c.st),
-            "H2D prevout outpoints");
-    HKV_TRY(hipMemcpyAsync(b + o_scr, prev_scripts + e0 * 2, n_ent * 8, hipMemcpyHostToDevice, c.st),
-            "H2D prevout scripts");
-    HKV_TRY(hipMemcpyAsync(b + o_val, prev_values + e0, n_ent * 8, hipMemcpyHostToDevice, c.st), "H2D prevout values");
-  }
-  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
-  // the input total sizes the scratch: counted on the device, read back once
-  // (the count's own status bit is dropped: the total is not known before it)
-  uint32_t total = 0;
-  HKV_TRY(hkv::launch_stdtx_counts(dt.bytes, dt.offsets, dt.n_tx, 0, d.std_first, status, c.st), "input count launch");
-  HKV_TRY(hipMemcpyAsync(&total, d.std_first + n_tx, sizeof(total), hipMemcpyDeviceToHost, c.st), "D2H input total");
-  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
-  HKV_TRY(hipStreamSynchronize(c.st), "input count sync");
-  const size_t n = total;
-  if (n > HKV_MAX_STD_INPUTS) return c.done(HKV_E_ARG);
-  HKV_RC(d.std_jobs.reserve(n, "hipMalloc(jobs)"));
-  HKV_RC(d.recs.reserve(n * hkv::REC_SIZE, "hipMalloc(records)"));
-  HKV_RC(d.host_std_bits.reserve((n + 63) / 64 * 2, "hipMalloc(verdict words)"));
-  HKV_RC(enqueue_verify_std_txs(c, &dt, p, forkid, n, d.std_first, d.std_jobs, d.recs, d.host_std_bits,
-                                d.host_tx_bits, status, true));
-  // (the tx words come in pairs per 64 txs; the caller gets ceil(n_tx/32))
-  HKV_TRY(hipMemcpyAsync(tx_verdict_bits, d.host_tx_bits, (n_tx + 31) / 32 * 4, hipMemcpyDeviceToHost, c.st),
-          "D2H tx bits");
-  uint32_t fault = 0;
-  HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
-  HKV_TRY(hipStreamSynchronize(c.st), "std txs sync");
-  if (fault & HKV_STATUS_TAIL_FAULT) {
-    g_last_hip = "multisig tail: work-queue wait timed out";
-    return c.done(HKV_E_INTERNAL);
-  }
-  return c.done();
-}
-
-// ---- in-batch prevouts: hkv_verify_block_txs ----------------------------------
+// ---- in-batch prevouts: the txid table and the block job builder ---------------
 
 size_t hkv_txid_table_slots(size_t n_tx) { return n_tx < 0xFFFFFF00ull ? hkv::txid_table_slots(n_tx) : 0; }
 
@@ -1866,21 +1766,77 @@ int hkv_block_tx_jobs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const 
                             d_jobs, d_input_src, d_status, false);
 }
 
-// the stages of hkv_verify_block_txs* on c's stream (the caller holds the Tx
-// lock and has acquired the scratch with status as the call's status word):
-// the block jobs, the unchanged per-input verify on the view that reads the
-// pool through the tx bytes, the per-tx reduction
-static int enqueue_verify_block_txs(Call& c, const hkv_txs* dt, const hkv::StdPrevouts& p, uint32_t pool_base,
-                                    int32_t forkid, size_t n_inputs, const hkv::TxidTable& tb, uint32_t* first,
-                                    hkv_input_job* jobs, uint32_t* src, void* recs, uint32_t* input_bits,
-                                    uint32_t* tx_bits, uint32_t* status, bool counted) {
-  HKV_RC(enqueue_block_jobs(c.st, dt, p, pool_base, n_inputs, tb, first, jobs, src, status, counted));
+// ---- the composed verify of whole txs: hkv_verify_std_txs*, hkv_verify_block_txs* ----
+
+// what the block forms add to the composed verify's operands
+struct BlockPart {
+  hkv::TxidTable tb;   // the txids (written here) and their table
+  uint32_t* src;       // a src word per input
+  uint32_t pool_base;  // where the pool starts, counted from the tx bytes (block_pool_ok)
+};
+// the operands of enqueue_verify_txs, filled by field name by its four callers
+struct TxVerify {
+  const hkv_txs* txs = nullptr;
+  hkv::StdPrevouts prevouts{};
+  int32_t forkid = -1;
+  size_t n_inputs = 0;
+  uint32_t* first = nullptr;  // n_tx + 1 input prefix sums
+  hkv_input_job* jobs = nullptr;
+  void* recs = nullptr;
+  uint32_t* input_bits = nullptr;
+  uint32_t* tx_bits = nullptr;
+  uint32_t* status = nullptr;        // the call's status word
+  bool counted = false;              // the caller ran the input count: first holds the sums
+  const BlockPart* block = nullptr;  // or null: the std forms
+};
+
+// The stages of batch verifyStdTx on c's stream (the caller holds the Tx lock
+// and has acquired the scratch with v.status as the call's status word): the
+// job builder — the std one, or with v.block the block one behind the txids
+// and their table —, the unchanged per-input verify — for a block on the view
+// that reads the pool through the tx bytes —, the per-tx reduction.
+static int enqueue_verify_txs(Call& c, const TxVerify& v) {
+  const hkv_txs* dt = v.txs;
   hkv_txs view = *dt;
-  view.scripts = dt->bytes;
-  view.scripts_len = pool_base + dt->scripts_len;
-  if (n_inputs) HKV_RC(enqueue_verify_std_inputs(c.d, &view, jobs, n_inputs, forkid, recs, input_bits, c.st));
-  HKV_TRY(hkv::launch_tx_verdicts(first, dt->n_tx, input_bits, status, tx_bits, c.st), "tx verdict launch");
+  if (v.block != nullptr) {
+    HKV_RC(enqueue_block_jobs(c.st, dt, v.prevouts, v.block->pool_base, v.n_inputs, v.block->tb, v.first, v.jobs,
+                              v.block->src, v.status, v.counted));
+    view.scripts = dt->bytes;
+    view.scripts_len = v.block->pool_base + dt->scripts_len;
+  } else {
+    if (!v.counted)
+      HKV_TRY(hkv::launch_stdtx_counts(dt->bytes, dt->offsets, dt->n_tx, (uint32_t)v.n_inputs, v.first, v.status, c.st),
+              "input count launch");
+    HKV_TRY(hkv::launch_stdtx_jobs(dt->bytes, dt->offsets, dt->n_tx, v.first, v.prevouts, (uint32_t)v.n_inputs, v.jobs,
+                                   c.st),
+            "job builder launch");
+  }
+  if (v.n_inputs)
+    HKV_RC(enqueue_verify_std_inputs(c.d, &view, v.jobs, v.n_inputs, v.forkid, v.recs, v.input_bits, c.st));
+  HKV_TRY(hkv::launch_tx_verdicts(v.first, dt->n_tx, v.input_bits, v.status, v.tx_bits, c.st), "tx verdict launch");
   return HKV_OK;
+}
+
+int hkv_verify_std_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
+                              const uint8_t* d_prev_outpoints, const uint32_t* d_prev_scripts,
+                              const uint64_t* d_prev_values, int32_t forkid, size_t n_inputs,
+                              uint32_t* d_input_first, hkv_input_job* d_jobs, void* d_records,
+                              uint32_t* d_input_bits, uint32_t* d_tx_bits, uint32_t* d_status, void* hip_stream) {
+  if (!dev_ok(ctx, dev) || !txs_ok(d_txs) || n_inputs > HKV_MAX_STD_INPUTS) return HKV_E_ARG;
+  if (d_txs->n_tx == 0) return HKV_OK;
+  if (!prevouts_ok(d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values) || !d_input_first ||
+      !d_tx_bits || !d_status || (n_inputs && (!d_jobs || !d_records || !d_input_bits)) ||
+      !aligned(d_input_first, 4) || !aligned(d_status, 4) || !aligned(d_jobs, 8) || !aligned(d_input_bits, 4) ||
+      !aligned(d_tx_bits, 4) || !aligned(d_txs->offsets, 4))
+    return HKV_E_ARG;
+  TxVerify v;
+  v.txs = d_txs, v.prevouts = hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values};
+  v.forkid = forkid, v.n_inputs = n_inputs, v.first = d_input_first, v.jobs = d_jobs, v.recs = d_records;
+  v.input_bits = d_input_bits, v.tx_bits = d_tx_bits, v.status = d_status;
+  Call c(ctx, dev, hip_stream, Lock::Tx);
+  int rc = c.acquire(d_status);
+  if (!rc) rc = enqueue_verify_txs(c, v);
+  return c.done(rc);
 }
 
 int hkv_verify_block_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, const uint32_t* d_prev_offsets,
@@ -1898,17 +1854,78 @@ int hkv_verify_block_txs_device(hkv_ctx* ctx, int dev, const hkv_txs* d_txs, con
       !aligned(d_input_first, 4) || !aligned(d_status, 4) || !aligned(d_jobs, 8) || !aligned(d_input_src, 4) ||
       !aligned(d_input_bits, 4) || !aligned(d_tx_bits, 4) || !aligned(d_txs->offsets, 4))
     return HKV_E_ARG;
-  const hkv::TxidTable tb = txid_table(ctx, dev, d_txids, d_txs->n_tx, d_table, n_slots);
+  const BlockPart blk{txid_table(ctx, dev, d_txids, d_txs->n_tx, d_table, n_slots), d_input_src, base};
+  TxVerify v;
+  v.txs = d_txs, v.prevouts = hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values};
+  v.forkid = forkid, v.n_inputs = n_inputs, v.first = d_input_first, v.jobs = d_jobs, v.recs = d_records;
+  v.input_bits = d_input_bits, v.tx_bits = d_tx_bits, v.status = d_status, v.block = &blk;
   Call c(ctx, dev, hip_stream, Lock::Tx);
   int rc = c.acquire(d_status);
-  if (!rc)
-    rc = enqueue_verify_block_txs(c, d_txs,
-                                  hkv::StdPrevouts{d_prev_offsets, d_prev_outpoints, d_prev_scripts, d_prev_values},
-                                  base, forkid, n_inputs, tb, d_input_first, d_jobs, d_input_src, d_records,
-                                  d_input_bits, d_tx_bits, d_status, false);
+  if (!rc) rc = enqueue_verify_txs(c, v);
   return c.done(rc);
 }
 
+// The block forms' tx staging: the tx bytes, rounded up to 4 (pool_at), and
+// the pool behind them in one buffer. (The std form keeps the pool in a buffer
+// of its own: stage_txs.)
+static int stage_block_txs(Call& c, const hkv_txs* h, size_t pool_at, hkv_txs* dt) {
+  DevCtx& d = c.d;
+  const size_t n_tx = h->n_tx, nbytes = h->offsets[n_tx];
+  HKV_RC(d.stage_tx_bytes.reserve(pool_at + h->scripts_len, "hipMalloc(tx bytes and pool)"));
+  HKV_RC(d.stage_tx_off.reserve(n_tx + 1, "hipMalloc(tx offsets)"));
+  uint8_t* b = d.stage_tx_bytes;
+  if (nbytes) HKV_TRY(hipMemcpyAsync(b, h->bytes, nbytes, hipMemcpyHostToDevice, c.st), "H2D txs");
+  HKV_TRY(hipMemcpyAsync(d.stage_tx_off, h->offsets, (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D offsets");
+  if (h->scripts_len)
+    HKV_TRY(hipMemcpyAsync(b + pool_at, h->scripts, h->scripts_len, hipMemcpyHostToDevice, c.st), "H2D scripts");
+  *dt = hkv_txs{b, d.stage_tx_off, (uint32_t)n_tx, b + pool_at, h->scripts_len};
+  return HKV_OK;
+}
+
+// The prevout lists of a host form in stage_prev, as pl lays them out
+// (hkv_plan.h plan_prevouts: only the entries the offsets name, the offsets
+// rebased by the first); *p: the staged arrays.
+static int stage_prevouts(Call& c, const hkv::PrevoutPlan& pl, const uint8_t* outpoints, const uint32_t* scripts,
+                          const uint64_t* values, hkv::StdPrevouts* p) {
+  HKV_RC(c.d.stage_prev.reserve(pl.total, "hipMalloc(prevouts)"));
+  uint8_t* b = c.d.stage_prev;
+  HKV_TRY(hipMemcpyAsync(b + pl.o_off, pl.rebased.data(), pl.rebased.size() * 4, hipMemcpyHostToDevice, c.st),
+          "H2D prevout offsets");
+  if (pl.n_ent) {
+    HKV_TRY(hipMemcpyAsync(b + pl.o_op, outpoints + pl.e0 * 36, pl.n_ent * 36, hipMemcpyHostToDevice, c.st),
+            "H2D prevout outpoints");
+    HKV_TRY(hipMemcpyAsync(b + pl.o_scr, scripts + pl.e0 * 2, pl.n_ent * 8, hipMemcpyHostToDevice, c.st),
+            "H2D prevout scripts");
+    HKV_TRY(hipMemcpyAsync(b + pl.o_val, values + pl.e0, pl.n_ent * 8, hipMemcpyHostToDevice, c.st),
+            "H2D prevout values");
+  }
+  *p = hkv::StdPrevouts{reinterpret_cast<const uint32_t*>(b + pl.o_off), b + pl.o_op,
+                        reinterpret_cast<const uint32_t*>(b + pl.o_scr),
+                        reinterpret_cast<const uint64_t*>(b + pl.o_val)};
+  return HKV_OK;
+}
+
+// The input total sizes a host form's scratch: counted on the device into
+// std_first (reserved by the caller), read back once into *n, waited for. The
+// count's own status bit is dropped (the total is not known before it) by
+// zeroing the call's status word behind it; none is needed in front: the count
+// only ORs into the word (hkv_stdtx.hip hkv_stdtx_scan_kernel), nothing reads it.
+static int count_inputs(Call& c, const hkv_txs& dt, uint32_t* status, size_t* n) {
+  uint32_t total = 0;
+  HKV_TRY(hkv::launch_stdtx_counts(dt.bytes, dt.offsets, dt.n_tx, 0, c.d.std_first, status, c.st), "input count launch");
+  HKV_TRY(hipMemcpyAsync(&total, c.d.std_first + dt.n_tx, sizeof(total), hipMemcpyDeviceToHost, c.st), "D2H input total");
+  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
+  HKV_TRY(hipStreamSynchronize(c.st), "input count sync");
+  *n = total;
+  return HKV_OK;
+}
+
+// what the host forms of hkv_verify_block_txs* add to hkv_verify_std_txs' output
+struct HostBlock {
+  uint32_t* input_first;  // or null
+  uint32_t* input_src;    // or null
+  size_t input_cap;       // the room of input_src and HostSpends::input_spender
+};
 // what the host form of the spend stage adds to hkv_verify_block_txs' outputs
 struct HostSpends {
   uint64_t max_money;
@@ -1917,72 +1934,40 @@ struct HostSpends {
   uint8_t* tx_flags;
 };
 
-// hkv_verify_block_txs, and with sp its spend stage behind it on the same
-// stream (hkv_verify_block_txs_spends): one staging, one readback of the input
-// total, one final wait
-static int verify_block_txs_host(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
-                                 const uint8_t* prev_outpoints, const uint32_t* prev_scripts,
-                                 const uint64_t* prev_values, int32_t forkid, uint32_t* tx_verdict_bits,
-                                 uint32_t* input_first, uint32_t* input_src, size_t input_src_cap,
-                                 const HostSpends* sp) {
+// The blocking host forms: hkv_verify_std_txs, with blk hkv_verify_block_txs,
+// and with sp its spend stage behind it on the same stream
+// (hkv_verify_block_txs_spends): one staging, one readback of the input
+// total, one final wait.
+static int verify_txs_host(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                           const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                           int32_t forkid, uint32_t* tx_verdict_bits, const HostBlock* blk, const HostSpends* sp) {
   if (!ctx || ctx->devs.empty() || !txs_ok(txs)) return HKV_E_ARG;
   const size_t n_tx = txs->n_tx;
   if (n_tx == 0) return HKV_OK;
   if (!prev_offsets || !tx_verdict_bits || !tx_offsets_sorted(txs)) return HKV_E_ARG;
-  for (size_t t = 0; t < n_tx; ++t)
-    if (prev_offsets[t + 1] < prev_offsets[t]) return HKV_E_ARG;
-  const size_t e0 = prev_offsets[0], n_ent = prev_offsets[n_tx] - e0;
-  if (n_ent && (!prev_outpoints || !prev_scripts || !prev_values)) return HKV_E_ARG;
-  // the tx bytes, rounded up to 4, and the pool behind them in one buffer
-  const size_t nbytes = txs->offsets[n_tx], pool_at = round_up(nbytes, 4);
-  const size_t n_slots = hkv::txid_table_slots(n_tx);
-  if (pool_at + txs->scripts_len > 0xFFFFFFFFull || n_slots > 0x80000000ull) return HKV_E_ARG;
+  const hkv::PrevoutPlan plan = hkv::plan_prevouts(prev_offsets, n_tx, prev_outpoints && prev_scripts && prev_values);
+  if (!plan.ok) return HKV_E_ARG;
+  // a block: the pool goes behind the tx bytes, in one range of less than 2^32 bytes
+  const size_t pool_at = round_up(txs->offsets[n_tx], 4), n_slots = blk ? hkv::txid_table_slots(n_tx) : 0;
+  if (blk && (pool_at + txs->scripts_len > 0xFFFFFFFFull || n_slots > 0x80000000ull)) return HKV_E_ARG;
   Call c(ctx, 0, Lock::Tx);
   DevCtx& d = c.d;
   uint32_t* status = reinterpret_cast<uint32_t*>(d.ms_bar + MS_HOST_STATUS);
-  // one staging buffer: values | entry offsets | script references | outpoints
-  // (the entries the offsets name, the offsets rebased by the first)
-  hkv::Layout l;
-  const size_t o_val = l.add(n_ent * 8, 8), o_off = l.add((n_tx + 1) * 4, 4), o_scr = l.add(n_ent * 8, 4),
-               o_op = l.add(n_ent * 36, 4);
-  std::vector<uint32_t> rebased(n_tx + 1);
-  for (size_t t = 0; t <= n_tx; ++t) rebased[t] = (uint32_t)(prev_offsets[t] - e0);
+  hkv_txs dt;
+  TxVerify v;
   HKV_RC(c.acquire(status));
-  HKV_RC(d.stage_tx_bytes.reserve(pool_at + txs->scripts_len, "hipMalloc(tx bytes and pool)"));
-  HKV_RC(d.stage_tx_off.reserve(n_tx + 1, "hipMalloc(tx offsets)"));
-  HKV_RC(d.stage_prev.reserve(l.total, "hipMalloc(prevouts)"));
+  if (blk) HKV_RC(stage_block_txs(c, txs, pool_at, &dt));
+  else HKV_RC(stage_txs(d, txs, nullptr, 0, &dt));
   HKV_RC(d.std_first.reserve(n_tx + 1, "hipMalloc(input offsets)"));
   HKV_RC(d.host_tx_bits.reserve((n_tx + 63) / 64 * 2, "hipMalloc(tx verdict words)"));
-  HKV_RC(d.blk_txids.reserve(n_tx * 32, "hipMalloc(txids)"));
-  HKV_RC(d.blk_table.reserve(n_slots, "hipMalloc(txid table)"));
-  uint8_t* tb_bytes = d.stage_tx_bytes;
-  if (nbytes) HKV_TRY(hipMemcpyAsync(tb_bytes, txs->bytes, nbytes, hipMemcpyHostToDevice, c.st), "H2D txs");
-  HKV_TRY(hipMemcpyAsync(d.stage_tx_off, txs->offsets, (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D offsets");
-  if (txs->scripts_len)
-    HKV_TRY(hipMemcpyAsync(tb_bytes + pool_at, txs->scripts, txs->scripts_len, hipMemcpyHostToDevice, c.st),
-            "H2D scripts");
-  const hkv_txs dt{tb_bytes, d.stage_tx_off, (uint32_t)n_tx, tb_bytes + pool_at, txs->scripts_len};
-  uint8_t* b = d.stage_prev;
-  const hkv::StdPrevouts p{reinterpret_cast<const uint32_t*>(b + o_off), b + o_op,
-                           reinterpret_cast<const uint32_t*>(b + o_scr),
-                           reinterpret_cast<const uint64_t*>(b + o_val)};
-  HKV_TRY(hipMemcpyAsync(b + o_off, rebased.data(), (n_tx + 1) * 4, hipMemcpyHostToDevice, c.st), "H2D prevout offsets");
-  if (n_ent) {
-    HKV_TRY(hipMemcpyAsync(b + o_op, prev_outpoints + e0 * 36, n_ent * 36, hipMemcpyHostToDevice, c.st),
-            "H2D prevout outpoints");
-    HKV_TRY(hipMemcpyAsync(b + o_scr, prev_scripts + e0 * 2, n_ent * 8, hipMemcpyHostToDevice, c.st),
-            "H2D prevout scripts");
-    HKV_TRY(hipMemcpyAsync(b + o_val, prev_values + e0, n_ent * 8, hipMemcpyHostToDevice, c.st), "H2D prevout values");
+  if (blk) {
+    HKV_RC(d.blk_txids.reserve(n_tx * 32, "hipMalloc(txids)"));
+    HKV_RC(d.blk_table.reserve(n_slots, "hipMalloc(txid table)"));
   }
-  // the input total sizes the scratch: counted on the device, read back once
-  // (the count's own status bit is dropped: the total is not known before it)
-  uint32_t total = 0;
-  HKV_TRY(hkv::launch_stdtx_counts(dt.bytes, dt.offsets, dt.n_tx, 0, d.std_first, status, c.st), "input count launch");
-  HKV_TRY(hipMemcpyAsync(&total, d.std_first + n_tx, sizeof(total), hipMemcpyDeviceToHost, c.st), "D2H input total");
-  HKV_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), c.st), "hipMemset(call status)");
-  HKV_TRY(hipStreamSynchronize(c.st), "input count sync");
-  const size_t n = total;
-  if (n > HKV_MAX_STD_INPUTS || ((input_src || (sp && sp->input_spender)) && n > input_src_cap))
+  HKV_RC(stage_prevouts(c, plan, prev_outpoints, prev_scripts, prev_values, &v.prevouts));
+  size_t n = 0;
+  HKV_RC(count_inputs(c, dt, status, &n));
+  if (n > HKV_MAX_STD_INPUTS || (blk && (blk->input_src || (sp && sp->input_spender)) && n > blk->input_cap))
     return c.done(HKV_E_ARG);
   const size_t spend_slots = sp ? hkv::spend_table_slots(n) : 0;
   if (sp) {
@@ -1994,19 +1979,25 @@ static int verify_block_txs_host(hkv_ctx* ctx, const hkv_txs* txs, const uint32_
     HKV_RC(d.spd_flags.reserve(n_tx, "hipMalloc(tx flags)"));
   }
   HKV_RC(d.std_jobs.reserve(n, "hipMalloc(jobs)"));
-  HKV_RC(d.blk_src.reserve(n, "hipMalloc(input src)"));
+  if (blk) HKV_RC(d.blk_src.reserve(n, "hipMalloc(input src)"));
   HKV_RC(d.recs.reserve(n * hkv::REC_SIZE, "hipMalloc(records)"));
   HKV_RC(d.host_std_bits.reserve((n + 63) / 64 * 2, "hipMalloc(verdict words)"));
-  const hkv::TxidTable tb{reinterpret_cast<const uint32_t*>(d.blk_txids.get()), (uint32_t)n_tx, d.blk_table,
-                          (uint32_t)n_slots, ctx->txid_salt, d.txid_mask};
-  HKV_RC(enqueue_verify_block_txs(c, &dt, p, (uint32_t)pool_at, forkid, n, tb, d.std_first, d.std_jobs, d.blk_src,
-                                  d.recs, d.host_std_bits, d.host_tx_bits, status, true));
+  // (operands taken after the reserves above, which may move the scratch)
+  const BlockPart part{hkv::TxidTable{reinterpret_cast<const uint32_t*>(d.blk_txids.get()), (uint32_t)n_tx, d.blk_table,
+                                      (uint32_t)n_slots, ctx->txid_salt, d.txid_mask},
+                       d.blk_src, (uint32_t)pool_at};
+  v.txs = &dt, v.forkid = forkid, v.n_inputs = n, v.first = d.std_first, v.jobs = d.std_jobs, v.recs = d.recs;
+  v.input_bits = d.host_std_bits, v.tx_bits = d.host_tx_bits, v.status = status, v.counted = true;
+  v.block = blk ? &part : nullptr;
+  HKV_RC(enqueue_verify_txs(c, v));
   // (the tx words come in pairs per 64 txs; the caller gets ceil(n_tx/32))
   HKV_TRY(hipMemcpyAsync(tx_verdict_bits, d.host_tx_bits, (n_tx + 31) / 32 * 4, hipMemcpyDeviceToHost, c.st),
           "D2H tx bits");
-  if (input_first)
-    HKV_TRY(hipMemcpyAsync(input_first, d.std_first, (n_tx + 1) * 4, hipMemcpyDeviceToHost, c.st), "D2H input offsets");
-  if (input_src && n) HKV_TRY(hipMemcpyAsync(input_src, d.blk_src, n * 4, hipMemcpyDeviceToHost, c.st), "D2H input src");
+  if (blk && blk->input_first)
+    HKV_TRY(hipMemcpyAsync(blk->input_first, d.std_first, (n_tx + 1) * 4, hipMemcpyDeviceToHost, c.st),
+            "D2H input offsets");
+  if (blk && blk->input_src && n)
+    HKV_TRY(hipMemcpyAsync(blk->input_src, d.blk_src, n * 4, hipMemcpyDeviceToHost, c.st), "D2H input src");
   if (sp) {
     const hkv::SpendStage stage{dt.bytes,      dt.offsets,  dt.n_tx,     d.std_first,   d.std_jobs,
                                 d.blk_src,     (uint32_t)n, sp->max_money, d.spd_off,   d.spd_table,
@@ -2018,22 +2009,23 @@ static int verify_block_txs_host(hkv_ctx* ctx, const hkv_txs* txs, const uint32_
     if (sp->tx_sums) HKV_TRY(hipMemcpyAsync(sp->tx_sums, d.spd_sums, 2 * n_tx * 8, hipMemcpyDeviceToHost, c.st), "D2H tx sums");
     HKV_TRY(hipMemcpyAsync(sp->tx_flags, d.spd_flags, n_tx, hipMemcpyDeviceToHost, c.st), "D2H tx flags");
   }
-  uint32_t fault = 0;
-  HKV_TRY(hipMemcpyAsync(&fault, status, sizeof(fault), hipMemcpyDeviceToHost, c.st), "D2H call status");
-  HKV_TRY(hipStreamSynchronize(c.st), "block txs sync");
-  if (fault & HKV_STATUS_TAIL_FAULT) {
-    g_last_hip = "multisig tail: work-queue wait timed out";
-    return c.done(HKV_E_INTERNAL);
-  }
-  return c.done();
+  return finish_status_call(c, status, blk ? "block txs sync" : "std txs sync");
+}
+
+int hkv_verify_std_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
+                       const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
+                       int32_t forkid, uint32_t* tx_verdict_bits) {
+  return verify_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid, tx_verdict_bits,
+                         nullptr, nullptr);
 }
 
 int hkv_verify_block_txs(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t* prev_offsets,
                          const uint8_t* prev_outpoints, const uint32_t* prev_scripts, const uint64_t* prev_values,
                          int32_t forkid, uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
                          size_t input_src_cap) {
-  return verify_block_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid,
-                               tx_verdict_bits, input_first, input_src, input_src_cap, nullptr);
+  const HostBlock blk{input_first, input_src, input_src_cap};
+  return verify_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid, tx_verdict_bits,
+                         &blk, nullptr);
 }
 
 // ---- whole-block spend checks: hkv_block_spends_device -------------------------
@@ -2082,9 +2074,10 @@ int hkv_verify_block_txs_spends(hkv_ctx* ctx, const hkv_txs* txs, const uint32_t
                                 uint32_t* tx_verdict_bits, uint32_t* input_first, uint32_t* input_src,
                                 uint32_t* input_spender, size_t input_cap, uint64_t* tx_sums, uint8_t* tx_flags) {
   if (!tx_flags || max_money >= hkv::SPEND_MONEY_LIMIT) return HKV_E_ARG;
+  const HostBlock blk{input_first, input_src, input_cap};
   const HostSpends sp{max_money, input_spender, tx_sums, tx_flags};
-  return verify_block_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid,
-                               tx_verdict_bits, input_first, input_src, input_cap, &sp);
+  return verify_txs_host(ctx, txs, prev_offsets, prev_outpoints, prev_scripts, prev_values, forkid, tx_verdict_bits,
+                         &blk, &sp);
 }
 
 // ---- header chain context: hkv_chain_context_device, hkv_connect_headers* -------
@@ -2130,6 +2123,18 @@ bool chain_ptrs_ok(const uint8_t* d_headers, const uint8_t* d_hashes, const uint
          aligned(d_cp_heights, 4) && aligned(d_cp_hashes, 4) && aligned(d_mtp, 4) && aligned(d_bits, 4) &&
          aligned(d_work, 16) && aligned(d_scratch, 4);
 }
+
+// the stage's arrays (s.ctx is chain_ctx_of's); hdr_status and first_bad:
+// both, or neither for the stage without the first-bad reduction
+// (static: a function of this extern "C" block is exported even from an unnamed namespace)
+static void chain_stage_arrays(hkv::ChainStage& s, const uint8_t* headers, size_t n, const uint8_t* hashes,
+                        const uint32_t* cp_heights, const uint8_t* cp_hashes, size_t n_cp, uint32_t* mtp, uint32_t* bits,
+                        uint8_t* work, uint8_t* status, uint32_t* scratch, const uint8_t* hdr_status = nullptr,
+                        uint32_t* first_bad = nullptr) {
+  s.headers = headers, s.n = (uint32_t)n, s.hashes = hashes, s.cp_heights = cp_heights, s.cp_hashes = cp_hashes,
+  s.n_cp = (uint32_t)n_cp, s.mtp = mtp, s.bits = bits, s.work = reinterpret_cast<uint32_t*>(work), s.status = status,
+  s.scratch = scratch, s.hdr_status = hdr_status, s.first_bad = first_bad;
+}
 }  // namespace
 
 size_t hkv_chain_scratch_words(size_t n) { return hkv::chain_scratch_words(n); }
@@ -2153,9 +2158,8 @@ int hkv_chain_context_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, si
     return HKV_E_ARG;
   Call c(ctx, dev, hip_stream, Lock::None);
   HKV_RC(c.rc);
-  s.headers = d_headers, s.n = (uint32_t)n, s.hashes = d_hashes, s.cp_heights = d_cp_heights,
-  s.cp_hashes = d_cp_hashes, s.n_cp = (uint32_t)n_cp, s.mtp = d_mtp, s.bits = d_bits,
-  s.work = reinterpret_cast<uint32_t*>(d_work), s.status = d_status, s.scratch = d_scratch;
+  chain_stage_arrays(s, d_headers, n, d_hashes, d_cp_heights, d_cp_hashes, n_cp, d_mtp, d_bits, d_work, d_status,
+                     d_scratch);
   // (the stage hook is read without a lock, as hkv_block_spends_device reads its own)
   HKV_TRY(hkv::launch_chain_context(s, ctx->devs[(size_t)dev].chain_stages, c.st), "chain context launch");
   return HKV_OK;
@@ -2178,10 +2182,8 @@ int hkv_connect_headers_device(hkv_ctx* ctx, int dev, const uint8_t* d_headers, 
   HKV_RC(c.rc);
   HKV_TRY(hkv::launch_headers(d_headers, (uint32_t)n, d_pow_limit, d_prev_hash, d_hashes, d_hdr_status, c.st),
           "headers launch");
-  s.headers = d_headers, s.n = (uint32_t)n, s.hashes = d_hashes, s.cp_heights = d_cp_heights,
-  s.cp_hashes = d_cp_hashes, s.n_cp = (uint32_t)n_cp, s.mtp = d_mtp, s.bits = d_bits,
-  s.work = reinterpret_cast<uint32_t*>(d_work), s.status = d_status, s.scratch = d_scratch,
-  s.hdr_status = d_hdr_status, s.first_bad = d_first_bad;
+  chain_stage_arrays(s, d_headers, n, d_hashes, d_cp_heights, d_cp_hashes, n_cp, d_mtp, d_bits, d_work, d_status,
+                     d_scratch, d_hdr_status, d_first_bad);
   HKV_TRY(hkv::launch_chain_context(s, ctx->devs[(size_t)dev].chain_stages, c.st), "chain context launch");
   return HKV_OK;
 }
@@ -2218,12 +2220,9 @@ int hkv_connect_headers(hkv_ctx* ctx, const uint8_t* headers, size_t n, const ui
   HKV_TRY(hkv::launch_headers(b + o_h, (uint32_t)n, b + o_lim, prev_hash ? b + o_prev : nullptr, b + o_hash, b + o_st,
                               c.st),
           "headers launch");
-  s.headers = b + o_h, s.n = (uint32_t)n, s.hashes = b + o_hash,
-  s.cp_heights = reinterpret_cast<const uint32_t*>(b + o_cph), s.cp_hashes = b + o_cpx, s.n_cp = (uint32_t)n_cp,
-  s.mtp = reinterpret_cast<uint32_t*>(b + o_mtp), s.bits = reinterpret_cast<uint32_t*>(b + o_bits),
-  s.work = reinterpret_cast<uint32_t*>(b + o_work), s.status = b + o_cst,
-  s.scratch = reinterpret_cast<uint32_t*>(b + o_scr), s.hdr_status = b + o_st,
-  s.first_bad = reinterpret_cast<uint32_t*>(b + o_fb);
+  auto words = [b](size_t at) { return reinterpret_cast<uint32_t*>(b + at); };
+  chain_stage_arrays(s, b + o_h, n, b + o_hash, words(o_cph), b + o_cpx, n_cp, words(o_mtp), words(o_bits), b + o_work,
+                     b + o_cst, words(o_scr), b + o_st, words(o_fb));
   HKV_TRY(hkv::launch_chain_context(s, hkv::CHAIN_STAGE_ALL, c.st), "chain context launch");
   uint32_t first_bad = 0;
   HKV_TRY(hipMemcpyAsync(hashes_out, b + o_hash, n * 32, hipMemcpyDeviceToHost, c.st), "D2H header hashes");

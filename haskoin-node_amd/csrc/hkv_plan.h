@@ -1,6 +1,7 @@
 // hkv_plan.h — host-side shard planning, bitmap merging and device failover
 // for the multi-device entry points (hkv_api.cpp verify_from_host), the chunk
-// schedule of a shard and the layout of the one-buffer host forms. Pure C++
+// schedule of a shard, the layout of the one-buffer host forms and the
+// staging plan of the verifyStdTx forms' prevout lists. Pure C++
 // (no HIP), so tests/host_plan.cpp drives exactly this code under ASan and
 // UBSan on the CPU.
 //
@@ -90,6 +91,47 @@ struct Layout {
     return at;
   }
 };
+
+// off[0 .. n] (n + 1 values) never step down: range k = [off[k], off[k + 1])
+// is then well formed and lies inside [off[0], off[n]).
+inline bool offsets_nondecreasing(const uint32_t* off, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (off[k + 1] < off[k]) return false;
+  return true;
+}
+
+// The staging of a batch's prevout lists by the host forms of batch
+// verifyStdTx (hkv_api.cpp stage_prevouts). The caller's arrays may start at
+// any entry: only the n_ent entries from e0 on, which the offsets name, are
+// staged, so the staged offsets are rebased by e0. One buffer of total bytes:
+// values (8 B an entry, 8-aligned) | the n_tx + 1 entry offsets | script
+// references (8 B) | outpoints (36 B), each of the last three 4-aligned.
+// ok: the call is acceptable — the offsets do not decrease, and the three
+// entry arrays are there (have_entries) unless no entry is named.
+struct PrevoutPlan {
+  bool ok = false;
+  size_t e0 = 0, n_ent = 0;
+  size_t o_val = 0, o_off = 0, o_scr = 0, o_op = 0, total = 0;
+  std::vector<uint32_t> rebased;  // n_tx + 1
+};
+inline PrevoutPlan plan_prevouts(const uint32_t* prev_offsets, size_t n_tx, bool have_entries) {
+  PrevoutPlan p;
+  if (!offsets_nondecreasing(prev_offsets, n_tx)) return p;
+  p.e0 = prev_offsets[0];
+  p.n_ent = prev_offsets[n_tx] - p.e0;
+  if (p.n_ent && !have_entries) return p;
+  Layout l;
+  p.o_val = l.add(p.n_ent * 8, 8);
+  p.o_off = l.add((n_tx + 1) * 4, 4);
+  p.o_scr = l.add(p.n_ent * 8, 4);
+  p.o_op = l.add(p.n_ent * 36, 4);
+  p.total = l.total;
+  std::vector<uint32_t> rebased(n_tx + 1);
+  for (size_t t = 0; t <= n_tx; ++t) rebased[t] = (uint32_t)(prev_offsets[t] - p.e0);
+  p.rebased = std::move(rebased);
+  p.ok = true;
+  return p;
+}
 
 // Only a HIP runtime error from the device's own streams, launches or
 // synchronisation (HKV_E_HIP = -4) says the device is bad. Allocation

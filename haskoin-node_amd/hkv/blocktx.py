@@ -20,10 +20,10 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .lib import HKV_SRC_LIST, HKV_SRC_NONE, HkvTxs, check
+from .lib import HKV_SRC_LIST, HKV_SRC_NONE, check
 from .records import unpack_bits
 from .sighash import TxBatch
-from .stdtx import Prevout, _forkid, _ptr, pack_prevouts
+from .stdtx import Prevout, _device_run, _forkid, _ptr, pack_prevouts
 
 
 def txid_table_slots(v, n_tx: int) -> int:
@@ -93,28 +93,45 @@ def _split(flat, first, n_tx):
     return [flat[int(first[t]): int(first[t + 1])] for t in range(n_tx)]
 
 
+class _HostCall:
+    """What the host forms of the block calls share: the batch as the C ABI
+    takes it (``head``: ctx, txs, the four prevout arrays) and the output
+    arrays of hkv_verify_block_txs (``outs``: tx words, input_first,
+    input_src; ``cap``: the room of input_src)."""
+
+    def __init__(self, verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]]):
+        if len(prevouts) != len(txs):
+            raise ValueError("one prevout list per tx")
+        self.n_tx = n_tx = len(txs)
+        tb = TxBatch(txs)
+        packed = pack_prevouts(tb, prevouts)
+        st, pool = tb.struct()
+        self._keep = (tb, packed, st, pool)
+        self.head = (verifier.ctx, ctypes.byref(st)) + tuple(a.ctypes.data for a in packed)
+        self.words = np.zeros(max(1, (n_tx + 31) // 32), dtype=np.uint32)
+        self.first = np.zeros(n_tx + 1, dtype=np.uint32)
+        self.cap = int(tb.offsets[-1]) // 41 + 1   # (an input is at least 41 bytes of its tx)
+        self.src = np.zeros(self.cap, dtype=np.uint32)
+        self.outs = (self.words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), self.first.ctypes.data,
+                     self.src.ctypes.data)
+
+    def tx_ok(self) -> List[bool]:
+        return unpack_bits(self.words, self.n_tx).tolist()
+
+    def srcs(self) -> List[List[int]]:
+        return _split(self.src.tolist(), self.first, self.n_tx)
+
+
 def verify_block_txs_host(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]],
                           forkid: Optional[int] = None) -> Tuple[List[bool], List[List[int]]]:
     """hkv_verify_block_txs (the host form, first device, blocking):
     ([tx verdict], [[src of input i of tx t]])."""
-    if len(prevouts) != len(txs):
-        raise ValueError("one prevout list per tx")
-    n_tx = len(txs)
-    if n_tx == 0:
+    h = _HostCall(verifier, txs, prevouts)
+    if h.n_tx == 0:
         return [], []
-    tb = TxBatch(txs)
-    offsets, outpoints, scripts, values = pack_prevouts(tb, prevouts)
-    st, pool = tb.struct()
-    words = np.zeros(max(1, (n_tx + 31) // 32), dtype=np.uint32)
-    first = np.zeros(n_tx + 1, dtype=np.uint32)
-    cap = int(tb.offsets[-1]) // 41 + 1   # (an input is at least 41 bytes of its tx)
-    src = np.zeros(cap, dtype=np.uint32)
-    rc = verifier.lib.hkv_verify_block_txs(verifier.ctx, ctypes.byref(st), offsets.ctypes.data, outpoints.ctypes.data,
-                                           scripts.ctypes.data, values.ctypes.data, _forkid(forkid),
-                                           words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), first.ctypes.data,
-                                           src.ctypes.data, cap)
+    rc = verifier.lib.hkv_verify_block_txs(*h.head, _forkid(forkid), *h.outs, h.cap)
     check(rc, "hkv_verify_block_txs", verifier.lib)
-    return unpack_bits(words, n_tx).tolist(), _split(src.tolist(), first, n_tx)
+    return h.tx_ok(), h.srcs()
 
 
 def verify_block_txs(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]],
@@ -133,50 +150,11 @@ def verify_block_txs_detail(verifier, txs: Sequence[bytes], prevouts: Sequence[S
     Runs the device forms on torch-allocated buffers of the context's device
     ``dev`` (blocking): the count of hkv_std_tx_jobs_device with n_inputs = 0
     to learn the input total, then the composed call."""
-    import torch
-    from .stdtx import std_tx_jobs_device
-    if len(prevouts) != len(txs):
-        raise ValueError("one prevout list per tx")
-    n_tx = len(txs)
-    if n_tx == 0:
+    r = _device_run(verifier, txs, prevouts, forkid, dev, block=True)
+    if r is None:
         return [], [], []
-    tb = TxBatch(txs)
-    offsets, outpoints, scripts, values = pack_prevouts(tb, prevouts)
-    buf, pool_at = block_layout(tb)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
-
-    d_buf, d_off = up(buf), up(tb.offsets)
-    d_po, d_op, d_ps, d_pv = up(offsets), up(outpoints), up(scripts), up(values)
-    dt = HkvTxs(d_buf.data_ptr(), d_off.data_ptr(), n_tx, d_buf.data_ptr() + pool_at, tb._len)
-    first = torch.zeros(n_tx + 1, dtype=torch.int32, device="cuda")
-    status = torch.zeros(2, dtype=torch.int32, device="cuda")
-    std_tx_jobs_device(verifier, dev, dt, d_po.data_ptr(), d_op.data_ptr(), d_ps.data_ptr(), d_pv.data_ptr(), 0,
-                       first.data_ptr(), 0, status.data_ptr())
-    n = int(first[n_tx].item()) & 0xFFFFFFFF
-    status.zero_()
-    n_slots = txid_table_slots(verifier, n_tx)
-    txids = torch.zeros(n_tx * 32, dtype=torch.uint8, device="cuda")
-    table = torch.zeros(n_slots, dtype=torch.int32, device="cuda")
-    jobs = torch.zeros(max(1, n) * 24, dtype=torch.uint8, device="cuda")
-    src = torch.zeros(max(1, n), dtype=torch.int32, device="cuda")
-    recs = torch.zeros(max(1, n) * 168, dtype=torch.uint8, device="cuda")
-    bits = torch.zeros(max(1, (n + 63) // 64) * 2, dtype=torch.int32, device="cuda")
-    tx_bits = torch.zeros((n_tx + 63) // 64 * 2, dtype=torch.int32, device="cuda")
-    verify_block_txs_device(verifier, dev, dt, d_po.data_ptr(), d_op.data_ptr(), d_ps.data_ptr(), d_pv.data_ptr(),
-                            _forkid(forkid), n, txids.data_ptr(), table.data_ptr(), n_slots, first.data_ptr(),
-                            jobs.data_ptr(), src.data_ptr(), recs.data_ptr(), bits.data_ptr(), tx_bits.data_ptr(),
-                            status.data_ptr())
-    torch.cuda.synchronize()
-    st = int(status[0].item())
-    if st:
-        check(-5, f"hkv_verify_block_txs_device (status {st})")
-    f = first.cpu().numpy().view(np.uint32)
-    per_input = unpack_bits(bits.cpu().numpy().view(np.uint32), n).tolist()
-    srcs = src.cpu().numpy().view(np.uint32)[:n].tolist()
-    ok = unpack_bits(tx_bits.cpu().numpy().view(np.uint32), n_tx).tolist()
-    return ok, _split(per_input, f, n_tx), _split(srcs, f, n_tx)
+    n_tx = len(txs)
+    return r.tx_ok, _split(r.input_ok, r.first, n_tx), _split(r.src.tolist(), r.first, n_tx)
 
 
 __all__ = ["verify_block_txs", "verify_block_txs_host", "verify_block_txs_detail", "verify_block_txs_device",

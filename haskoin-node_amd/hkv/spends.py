@@ -17,12 +17,10 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .blocktx import _split, block_layout, txid_table_slots, verify_block_txs_device
+from .blocktx import _HostCall, _split
 from .lib import (HKV_SPEND_BALANCED, HKV_SPEND_COINBASE, HKV_SPEND_FIRST, HKV_SPEND_IN_RANGE, HKV_SPEND_OK,
-                  HKV_SPEND_OUT_RANGE, HKV_SPEND_RESOLVED, HkvTxs, check)
-from .records import unpack_bits
-from .sighash import TxBatch
-from .stdtx import Prevout, _forkid, _ptr, pack_prevouts
+                  HKV_SPEND_OUT_RANGE, HKV_SPEND_RESOLVED, check)
+from .stdtx import Prevout, _device_run, _forkid, _ptr
 
 SUM_NONE = 0xFFFFFFFFFFFFFFFF   # a sum whose RANGE flag is clear
 
@@ -60,33 +58,26 @@ def _pairs(spender, first, n_tx) -> List[List[Tuple[int, int]]]:
     return _split([(int(t), int(g - f[t])) for g, t in zip(flat, t_of)], first, n_tx)
 
 
+def _sum_pairs(sums, n_tx) -> List[Tuple[int, int]]:
+    return [(int(sums[2 * t]), int(sums[2 * t + 1])) for t in range(n_tx)]
+
+
 def verify_block_txs_spends_host(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]],
                                  forkid: Optional[int], max_money: int):
     """hkv_verify_block_txs_spends (the host form, first device, blocking):
     ([tx verdict], [[src]], [[spender as (tx, input)]], [(in_sum, out_sum)], [flags])."""
-    if len(prevouts) != len(txs):
-        raise ValueError("one prevout list per tx")
-    n_tx = len(txs)
+    h = _HostCall(verifier, txs, prevouts)
+    n_tx = h.n_tx
     if n_tx == 0:
         return [], [], [], [], []
-    tb = TxBatch(txs)
-    offsets, outpoints, scripts, values = pack_prevouts(tb, prevouts)
-    st, pool = tb.struct()
-    words = np.zeros(max(1, (n_tx + 31) // 32), dtype=np.uint32)
-    first = np.zeros(n_tx + 1, dtype=np.uint32)
-    cap = int(tb.offsets[-1]) // 41 + 1   # (an input is at least 41 bytes of its tx)
-    src = np.zeros(cap, dtype=np.uint32)
-    spender = np.zeros(cap, dtype=np.uint32)
+    spender = np.zeros(h.cap, dtype=np.uint32)
     sums = np.zeros(2 * n_tx, dtype=np.uint64)
     flags = np.zeros(n_tx, dtype=np.uint8)
-    rc = verifier.lib.hkv_verify_block_txs_spends(
-        verifier.ctx, ctypes.byref(st), offsets.ctypes.data, outpoints.ctypes.data, scripts.ctypes.data,
-        values.ctypes.data, _forkid(forkid), max_money, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-        first.ctypes.data, src.ctypes.data, spender.ctypes.data, cap, sums.ctypes.data, flags.ctypes.data)
+    rc = verifier.lib.hkv_verify_block_txs_spends(*h.head, _forkid(forkid), max_money, *h.outs, spender.ctypes.data,
+                                                  h.cap, sums.ctypes.data, flags.ctypes.data)
     check(rc, "hkv_verify_block_txs_spends", verifier.lib)
-    n = int(first[n_tx])
-    return (unpack_bits(words, n_tx).tolist(), _split(src.tolist(), first, n_tx), _pairs(spender[:n], first, n_tx),
-            [(int(sums[2 * t]), int(sums[2 * t + 1])) for t in range(n_tx)], flags.tolist())
+    n = int(h.first[n_tx])
+    return h.tx_ok(), h.srcs(), _pairs(spender[:n], h.first, n_tx), _sum_pairs(sums, n_tx), flags.tolist()
 
 
 def check_block_txs(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]],
@@ -98,65 +89,12 @@ def check_block_txs(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[
     (blocking): the count of hkv_std_tx_jobs_device with n_inputs = 0 to learn
     the input total, hkv_verify_block_txs_device, then
     hkv_block_spends_device on the same (null) stream."""
-    import torch
-    from .stdtx import std_tx_jobs_device
-    if len(prevouts) != len(txs):
-        raise ValueError("one prevout list per tx")
-    n_tx = len(txs)
-    if n_tx == 0:
+    r = _device_run(verifier, txs, prevouts, forkid, dev, block=True, max_money=max_money)
+    if r is None:
         return [], [], [], [], [], []
-    tb = TxBatch(txs)
-    offsets, outpoints, scripts, values = pack_prevouts(tb, prevouts)
-    buf, pool_at = block_layout(tb)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
-
-    d_buf, d_off = up(buf), up(tb.offsets)
-    d_po, d_op, d_ps, d_pv = up(offsets), up(outpoints), up(scripts), up(values)
-    dt = HkvTxs(d_buf.data_ptr(), d_off.data_ptr(), n_tx, d_buf.data_ptr() + pool_at, tb._len)
-    first = torch.zeros(n_tx + 1, dtype=torch.int32, device="cuda")
-    status = torch.zeros(2, dtype=torch.int32, device="cuda")
-    std_tx_jobs_device(verifier, dev, dt, d_po.data_ptr(), d_op.data_ptr(), d_ps.data_ptr(), d_pv.data_ptr(), 0,
-                       first.data_ptr(), 0, status.data_ptr())
-    n = int(first[n_tx].item()) & 0xFFFFFFFF
-    status.zero_()
-    n_slots = txid_table_slots(verifier, n_tx)
-    s_slots = spend_table_slots(verifier, n)
-    if s_slots == 0:
-        check(-1, "hkv_spend_table_slots (more than 2^30 inputs)")
-    m = max(1, n)
-    txids = torch.zeros(n_tx * 32, dtype=torch.uint8, device="cuda")
-    table = torch.zeros(n_slots, dtype=torch.int32, device="cuda")
-    jobs = torch.zeros(m * 24, dtype=torch.uint8, device="cuda")
-    src = torch.zeros(m, dtype=torch.int32, device="cuda")
-    recs = torch.zeros(m * 168, dtype=torch.uint8, device="cuda")
-    bits = torch.zeros(max(1, (n + 63) // 64) * 2, dtype=torch.int32, device="cuda")
-    tx_bits = torch.zeros((n_tx + 63) // 64 * 2, dtype=torch.int32, device="cuda")
-    in_off = torch.zeros(m, dtype=torch.int32, device="cuda")
-    s_table = torch.zeros(s_slots, dtype=torch.int32, device="cuda")
-    spender = torch.zeros(m, dtype=torch.int32, device="cuda")
-    sums = torch.zeros(2 * n_tx, dtype=torch.int64, device="cuda")
-    flags = torch.zeros(n_tx, dtype=torch.uint8, device="cuda")
-    verify_block_txs_device(verifier, dev, dt, d_po.data_ptr(), d_op.data_ptr(), d_ps.data_ptr(), d_pv.data_ptr(),
-                            _forkid(forkid), n, txids.data_ptr(), table.data_ptr(), n_slots, first.data_ptr(),
-                            jobs.data_ptr(), src.data_ptr(), recs.data_ptr(), bits.data_ptr(), tx_bits.data_ptr(),
-                            status.data_ptr())
-    block_spends_device(verifier, dev, dt, first.data_ptr(), jobs.data_ptr(), src.data_ptr(), n, max_money,
-                        in_off.data_ptr(), s_table.data_ptr(), s_slots, spender.data_ptr(), sums.data_ptr(),
-                        flags.data_ptr(), status.data_ptr())
-    torch.cuda.synchronize()
-    st = int(status[0].item())
-    if st:
-        check(-5, f"hkv_block_spends_device (status {st})")
-    f = first.cpu().numpy().view(np.uint32)
-    per_input = unpack_bits(bits.cpu().numpy().view(np.uint32), n).tolist()
-    srcs = src.cpu().numpy().view(np.uint32)[:n].tolist()
-    ok = unpack_bits(tx_bits.cpu().numpy().view(np.uint32), n_tx).tolist()
-    sm = sums.cpu().numpy().view(np.uint64)
-    return (ok, _split(per_input, f, n_tx), _split(srcs, f, n_tx),
-            _pairs(spender.cpu().numpy().view(np.uint32)[:n], f, n_tx),
-            [(int(sm[2 * t]), int(sm[2 * t + 1])) for t in range(n_tx)], flags.cpu().numpy().tolist())
+    n_tx = len(txs)
+    return (r.tx_ok, _split(r.input_ok, r.first, n_tx), _split(r.src.tolist(), r.first, n_tx),
+            _pairs(r.spender, r.first, n_tx), _sum_pairs(r.sums, n_tx), r.flags)
 
 
 __all__ = ["spend_table_slots", "block_spends_device", "verify_block_txs_spends_host", "check_block_txs",

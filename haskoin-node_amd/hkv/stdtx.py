@@ -110,6 +110,104 @@ def verify_std_txs_device(v, dev: int, d_txs, d_prev_offsets: int, d_prev_outpoi
     check(rc, "hkv_verify_std_txs_device", v.lib)
 
 
+JOB_BYTES, REC_BYTES = 24, 168   # hkv_input_job; a verify record
+
+
+def _pair_words(n_bits: int) -> int:
+    """The verdict words of n_bits verdicts: the kernels write a pair per 64."""
+    return (n_bits + 63) // 64 * 2
+
+
+def _device_run(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]], forkid: Optional[int],
+                dev: int, block: bool = False, max_money: Optional[int] = None):
+    """The composed device forms on torch-allocated buffers of the context's
+    device ``dev`` (blocking), behind verify_std_txs_detail, blocktx's
+    verify_block_txs_detail (``block``) and spends' check_block_txs
+    (``max_money``: the spend stage behind the block call on the same (null)
+    stream). Uploads the batch — the std form with the pool as its own
+    allocation, the block form behind the tx bytes (block_layout) —, runs
+    hkv_std_tx_jobs_device once with n_inputs = 0 to learn the input total,
+    sizes every buffer, runs the composed call, waits and checks the status
+    word. Returns None for an empty batch, else the host arrays: n, first
+    (uint32[n_tx + 1]), tx_ok and input_ok (lists of bool), and for a block
+    src, with max_money spender (uint32[n]), sums (uint64[2 n_tx]), flags."""
+    import torch
+    from types import SimpleNamespace
+    from .lib import HkvTxs
+    if len(prevouts) != len(txs):
+        raise ValueError("one prevout list per tx")
+    n_tx = len(txs)
+    if n_tx == 0:
+        return None
+    tb = TxBatch(txs)
+    packed = pack_prevouts(tb, prevouts)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
+
+    def zeros(count, dtype=torch.int32):
+        return torch.zeros(count, dtype=dtype, device="cuda")
+
+    def host(t, dtype=np.uint32):
+        return t.cpu().numpy().view(dtype)
+
+    d_off = up(tb.offsets)
+    if block:
+        from .blocktx import block_layout, txid_table_slots, verify_block_txs_device
+        buf, pool_at = block_layout(tb)
+        d_bytes = up(buf)
+        d_pool_ptr = d_bytes.data_ptr() + pool_at
+    else:
+        d_bytes, d_pool = up(tb.bytes), up(tb.struct()[1])
+        d_pool_ptr = d_pool.data_ptr()
+    dt = HkvTxs(d_bytes.data_ptr(), d_off.data_ptr(), n_tx, d_pool_ptr, tb._len)
+    d_prev = [up(a) for a in packed]
+    prev = [t.data_ptr() for t in d_prev]
+    first, status = zeros(n_tx + 1), zeros(2)
+    std_tx_jobs_device(verifier, dev, dt, *prev, 0, first.data_ptr(), 0, status.data_ptr())
+    n = int(first[n_tx].item()) & 0xFFFFFFFF
+    status.zero_()
+    m = max(1, n)
+    jobs, recs = zeros(m * JOB_BYTES, torch.uint8), zeros(m * REC_BYTES, torch.uint8)
+    bits, tx_bits = zeros(max(2, _pair_words(n))), zeros(_pair_words(n_tx))
+    out = SimpleNamespace(n=n)
+    if not block:
+        name = "hkv_verify_std_txs_device"
+        verify_std_txs_device(verifier, dev, dt, *prev, _forkid(forkid), n, first.data_ptr(), jobs.data_ptr(),
+                              recs.data_ptr(), bits.data_ptr(), tx_bits.data_ptr(), status.data_ptr())
+    else:
+        name = "hkv_verify_block_txs_device"
+        n_slots = txid_table_slots(verifier, n_tx)
+        txids, table, src = zeros(n_tx * 32, torch.uint8), zeros(n_slots), zeros(m)
+        if max_money is not None:
+            from .spends import block_spends_device, spend_table_slots
+            name = "hkv_block_spends_device"
+            s_slots = spend_table_slots(verifier, n)
+            if s_slots == 0:
+                check(-1, "hkv_spend_table_slots (more than 2^30 inputs)")
+            in_off, s_table, spender = zeros(m), zeros(s_slots), zeros(m)
+            sums, flags = zeros(2 * n_tx, torch.int64), zeros(n_tx, torch.uint8)
+        verify_block_txs_device(verifier, dev, dt, *prev, _forkid(forkid), n, txids.data_ptr(), table.data_ptr(),
+                                n_slots, first.data_ptr(), jobs.data_ptr(), src.data_ptr(), recs.data_ptr(),
+                                bits.data_ptr(), tx_bits.data_ptr(), status.data_ptr())
+        if max_money is not None:
+            block_spends_device(verifier, dev, dt, first.data_ptr(), jobs.data_ptr(), src.data_ptr(), n, max_money,
+                                in_off.data_ptr(), s_table.data_ptr(), s_slots, spender.data_ptr(), sums.data_ptr(),
+                                flags.data_ptr(), status.data_ptr())
+    torch.cuda.synchronize()
+    st = int(status[0].item())
+    if st:
+        check(-5, f"{name} (status {st})")
+    out.first = host(first)
+    out.input_ok = unpack_bits(host(bits), n).tolist()
+    out.tx_ok = unpack_bits(host(tx_bits), n_tx).tolist()
+    if block:
+        out.src = host(src)[:n]
+    if max_money is not None:
+        out.spender, out.sums, out.flags = host(spender)[:n], host(sums, np.uint64), host(flags, np.uint8).tolist()
+    return out
+
+
 def verify_std_txs_detail(verifier, txs: Sequence[bytes], prevouts: Sequence[Sequence[Prevout]],
                           forkid: Optional[int] = None, dev: int = 0) -> Tuple[List[bool], List[List[bool]]]:
     """verify_std_txs with the per-input verdicts the device form keeps
@@ -118,44 +216,10 @@ def verify_std_txs_detail(verifier, txs: Sequence[bytes], prevouts: Sequence[Seq
     inputs to name). Runs the device forms on torch-allocated buffers of the
     context's device ``dev`` (blocking): the prevout provider once with
     n_inputs = 0 to learn the batch's input total, then the composed call."""
-    import torch
-    if len(prevouts) != len(txs):
-        raise ValueError("one prevout list per tx")
-    n_tx = len(txs)
-    if n_tx == 0:
+    r = _device_run(verifier, txs, prevouts, forkid, dev)
+    if r is None:
         return [], []
-    from .lib import HkvTxs
-    tb = TxBatch(txs)
-    offsets, outpoints, scripts, values = pack_prevouts(tb, prevouts)
-    _, pool = tb.struct()
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
-
-    d_bytes, d_off, d_pool = up(tb.bytes), up(tb.offsets), up(pool)
-    d_po, d_op, d_ps, d_pv = up(offsets), up(outpoints), up(scripts), up(values)
-    dt = HkvTxs(d_bytes.data_ptr(), d_off.data_ptr(), n_tx, d_pool.data_ptr(), tb._len)
-    first = torch.zeros(n_tx + 1, dtype=torch.int32, device="cuda")
-    status = torch.zeros(2, dtype=torch.int32, device="cuda")
-    std_tx_jobs_device(verifier, dev, dt, d_po.data_ptr(), d_op.data_ptr(), d_ps.data_ptr(), d_pv.data_ptr(), 0,
-                       first.data_ptr(), 0, status.data_ptr())
-    n = int(first[n_tx].item()) & 0xFFFFFFFF
-    status.zero_()
-    jobs = torch.zeros(max(1, n) * 24, dtype=torch.uint8, device="cuda")
-    recs = torch.zeros(max(1, n) * 168, dtype=torch.uint8, device="cuda")
-    bits = torch.zeros(max(1, (n + 63) // 64) * 2, dtype=torch.int32, device="cuda")
-    tx_bits = torch.zeros((n_tx + 63) // 64 * 2, dtype=torch.int32, device="cuda")
-    verify_std_txs_device(verifier, dev, dt, d_po.data_ptr(), d_op.data_ptr(), d_ps.data_ptr(), d_pv.data_ptr(),
-                          _forkid(forkid), n, first.data_ptr(), jobs.data_ptr(), recs.data_ptr(), bits.data_ptr(),
-                          tx_bits.data_ptr(), status.data_ptr())
-    torch.cuda.synchronize()
-    st = int(status[0].item())
-    if st:
-        check(-5, f"hkv_verify_std_txs_device (status {st})")
-    f = first.cpu().numpy().view(np.uint32)
-    per_input = unpack_bits(bits.cpu().numpy().view(np.uint32), n).tolist()
-    ok = unpack_bits(tx_bits.cpu().numpy().view(np.uint32), n_tx).tolist()
-    return ok, [per_input[int(f[t]): int(f[t + 1])] for t in range(n_tx)]
+    return r.tx_ok, [r.input_ok[int(r.first[t]): int(r.first[t + 1])] for t in range(len(txs))]
 
 
 __all__ = ["verify_std_txs", "verify_std_txs_detail", "pack_prevouts", "std_tx_jobs_device", "tx_verdicts_device",

@@ -3,10 +3,12 @@
 // tests/test_host_plan.py with -fsanitize=address,undefined: the same header
 // the library compiles, driven by mock devices whose enqueue / join fail on
 // a random schedule; then the host-batch chunk schedule (host_chunks) and the
-// staging layout (Layout) of the same header. Prints "ok <cases>" or the
-// first failure and exits 1.
+// staging layout (Layout) of the same header, and the prevout staging plan of
+// the verifyStdTx host forms (plan_prevouts) against the arithmetic it
+// replaced. Prints "ok <cases>" or the first failure and exits 1.
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <random>
 #include <vector>
 
@@ -157,9 +159,131 @@ static bool check_layout(const std::vector<Part>& parts, size_t* total) {
   return true;
 }
 
+// The prevout staging as hkv_verify_std_txs and the block host form each wrote
+// it out before plan_prevouts: the acceptance rule, then the four parts one
+// behind the other (every size is a multiple of 4 and the values, 8 B each,
+// come first, so no part needs padding).
+struct HandStage {
+  bool ok = false;
+  size_t e0 = 0, n_ent = 0, o_val = 0, o_off = 0, o_scr = 0, o_op = 0, total = 0;
+};
+static HandStage stage_by_hand(const uint32_t* po, size_t n_tx, const uint8_t* ops, const uint32_t* scr,
+                               const uint64_t* val) {
+  HandStage h;
+  for (size_t t = 0; t < n_tx; ++t)
+    if (po[t + 1] < po[t]) return h;
+  h.e0 = po[0];
+  h.n_ent = po[n_tx] - h.e0;
+  if (h.n_ent && (!ops || !scr || !val)) return h;
+  h.o_val = 0;
+  h.o_off = h.n_ent * 8;
+  h.o_scr = h.o_off + (n_tx + 1) * 4;
+  h.o_op = h.o_scr + h.n_ent * 8;
+  h.total = h.o_op + h.n_ent * 36;
+  h.ok = true;
+  return h;
+}
+
+// one call: the plan against the hand staging; for an accepted call the
+// layout's own properties, then the copies stage_prevouts makes, from arrays
+// in heap blocks of their exact size into a block of exactly total bytes
+static bool check_prevout_plan(const std::vector<uint32_t>& offsets, bool with_entries, bool want_ok) {
+  const size_t n_tx = offsets.size() - 1;
+  std::unique_ptr<uint32_t[]> po(new uint32_t[n_tx + 1]);
+  std::copy(offsets.begin(), offsets.end(), po.get());
+  const size_t end = *std::max_element(offsets.begin(), offsets.end());  // entries [0, end) exist
+  std::unique_ptr<uint8_t[]> ops;
+  std::unique_ptr<uint32_t[]> scr;
+  std::unique_ptr<uint64_t[]> val;
+  if (with_entries) {
+    ops.reset(new uint8_t[end * 36]), scr.reset(new uint32_t[end * 2]), val.reset(new uint64_t[end]);
+    for (size_t k = 0; k < end * 36; ++k) ops[k] = (uint8_t)(k * 7 + 1);
+    for (size_t k = 0; k < end * 2; ++k) scr[k] = (uint32_t)(k * 0x9E3779B9u + 5);
+    for (size_t k = 0; k < end; ++k) val[k] = (uint64_t)k * 0x9E3779B97F4A7C15ull + 9;
+  }
+  const hkv::PrevoutPlan p = hkv::plan_prevouts(po.get(), n_tx, with_entries);
+  const HandStage h = stage_by_hand(po.get(), n_tx, ops.get(), scr.get(), val.get());
+  CHECK(p.ok == h.ok && p.ok == want_ok, "acceptance: plan %d hand %d want %d (n_tx=%zu)", (int)p.ok, (int)h.ok,
+        (int)want_ok, n_tx);
+  if (!p.ok) return true;
+  CHECK(p.e0 == h.e0 && p.n_ent == h.n_ent, "e0 %zu n_ent %zu, by hand %zu %zu", p.e0, p.n_ent, h.e0, h.n_ent);
+  CHECK(p.o_val == h.o_val && p.o_off == h.o_off && p.o_scr == h.o_scr && p.o_op == h.o_op && p.total == h.total,
+        "layout differs from the hand staging (n_tx=%zu e0=%zu n_ent=%zu)", n_tx, p.e0, p.n_ent);
+  const size_t at[4] = {p.o_val, p.o_off, p.o_scr, p.o_op}, align[4] = {8, 4, 4, 4};
+  const size_t bytes[4] = {p.n_ent * 8, (n_tx + 1) * 4, p.n_ent * 8, p.n_ent * 36};
+  for (int k = 0; k < 4; ++k) {
+    CHECK(at[k] % align[k] == 0, "part %d at %zu is not %zu-aligned", k, at[k], align[k]);
+    CHECK(k == 0 || at[k] >= at[k - 1] + bytes[k - 1], "part %d at %zu overlaps the one before", k, at[k]);
+  }
+  CHECK(p.total == at[3] + bytes[3], "total %zu is not the end of the last part", p.total);
+  CHECK(p.rebased.size() == n_tx + 1, "rebased holds %zu offsets", p.rebased.size());
+  for (size_t t = 0; t <= n_tx; ++t)
+    CHECK(p.rebased[t] == po[t] - p.e0, "rebased[%zu] = %u", t, p.rebased[t]);
+  // the copies, as stage_prevouts issues them
+  std::unique_ptr<uint8_t[]> stage(new uint8_t[p.total]);
+  std::memcpy(stage.get() + p.o_off, p.rebased.data(), p.rebased.size() * 4);
+  if (p.n_ent) {
+    std::memcpy(stage.get() + p.o_op, ops.get() + p.e0 * 36, p.n_ent * 36);
+    std::memcpy(stage.get() + p.o_scr, scr.get() + p.e0 * 2, p.n_ent * 8);
+    std::memcpy(stage.get() + p.o_val, val.get() + p.e0, p.n_ent * 8);
+  }
+  // what the device then reads: entry e of tx t's list, by the staged offsets
+  for (size_t t = 0; t < n_tx; ++t)
+    for (size_t e = p.rebased[t]; e < p.rebased[t + 1]; ++e) {
+      const size_t src = po[t] + (e - p.rebased[t]);
+      CHECK(std::memcmp(stage.get() + p.o_op + e * 36, ops.get() + src * 36, 36) == 0 &&
+                std::memcmp(stage.get() + p.o_scr + e * 8, scr.get() + src * 2, 8) == 0 &&
+                std::memcmp(stage.get() + p.o_val + e * 8, val.get() + src, 8) == 0,
+            "staged entry %zu of tx %zu is not the caller's entry %zu", e, t, src);
+    }
+  return true;
+}
+
+static bool check_prevout_plans(std::mt19937_64& rng, size_t* cases) {
+  for (size_t n_tx : {1ul, 2ul, 33ul})
+    for (uint32_t e0 : {0u, 1u, 7u}) {
+      for (int it = 0; it < 20; ++it) {
+        // it 0: every list empty; it 1: every list one entry; then lists of 0 to 3
+        std::vector<uint32_t> po(n_tx + 1, e0);
+        for (size_t t = 0; t < n_tx; ++t) po[t + 1] = po[t] + (it == 0 ? 0u : it == 1 ? 1u : (uint32_t)(rng() % 4));
+        const bool any = po[n_tx] != e0;
+        if (!check_prevout_plan(po, true, true)) return false;
+        if (!check_prevout_plan(po, false, !any)) return false;  // null entry arrays: only with no entry named
+        ++*cases;
+        if (it != 1) continue;
+        // one step down, at the first, a middle and the last position
+        for (size_t t : {(size_t)0, n_tx / 2, n_tx - 1}) {
+          std::vector<uint32_t> bad = po;
+          bad[t] = bad[t + 1] + 1;
+          if (!check_prevout_plan(bad, true, false)) return false;
+          ++*cases;
+        }
+      }
+    }
+  // sizes near the largest entry count, nothing allocated: no wrap, the hand sum
+  static_assert(sizeof(size_t) == 8, "the staging sizes need 64 bits");
+  for (uint32_t e0 : {0u, 1u}) {
+    const uint32_t po[2] = {e0, 0xFFFFFFFFu};
+    const hkv::PrevoutPlan p = hkv::plan_prevouts(po, 1, true);
+    const size_t n_ent = (size_t)0xFFFFFFFFu - e0;
+    CHECK(p.ok && p.e0 == e0 && p.n_ent == n_ent, "largest entry count: e0 %zu n_ent %zu", p.e0, p.n_ent);
+    CHECK(p.o_val == 0 && p.o_off == n_ent * 8 && p.o_scr == n_ent * 8 + 8 && p.o_op == n_ent * 16 + 8 &&
+              p.total == n_ent * 52 + 8 && p.total > (size_t)0xFFFFFFFFu * 50,
+          "largest entry count: total %zu", p.total);
+    CHECK(p.rebased.size() == 2 && p.rebased[0] == 0 && p.rebased[1] == n_ent, "largest entry count: rebased");
+    CHECK(!hkv::plan_prevouts(po, 1, false).ok, "largest entry count without entry arrays");
+    ++*cases;
+  }
+  return true;
+}
+
 int main() {
   std::mt19937_64 rng(0x504C414E);
   size_t cases = 0;
+  {
+    std::mt19937_64 prev_rng(0x50524556);  // (its own: the schedules below keep theirs)
+    if (!check_prevout_plans(prev_rng, &cases)) return 1;
+  }
   // the host-batch chunk schedule
   {
     const std::vector<size_t> pinned = {65536, 262144, 720896};

@@ -463,3 +463,100 @@ def test_no_in_batch_spends_is_verify_std_txs_bit_for_bit(torch, ver, world):
             assert tx.sum() == len(raws) - 1 and not tx[world.amount_tx]
         else:
             assert not tx.any()
+
+
+# --- the host forms' prevout arrays need not start at entry 0 -----------------------------------
+
+def _one_input_spend(rng, outpoint, kind, who, value, out_spk):
+    """A signed tx with one input of ``kind`` on ``outpoint`` and one output."""
+    tx = sh.Tx(2, [sh.TxIn(outpoint[:32], struct.unpack("<I", outpoint[32:])[0], b"", 0xFFFFFFFF)],
+               [sh.TxOut(value - 1000, out_spk)], [[]], 0)
+    bm._sign_input(rng, tx, 0, kind, who, value, None)
+    return sh.tx_serialize(tx)
+
+
+def test_host_forms_with_prevout_lists_that_start_past_entry_0(ver, coracle):
+    """hkv_verify_std_txs, hkv_verify_block_txs and hkv_verify_block_txs_spends
+    with prev_offsets[0] = 3: three entries no list names stand in front of
+    the lists' own, one of them the very prevout tx 1 lacks. Only the entries
+    the offsets name are staged, the offsets rebased: every output equals
+    that of the call whose arrays start at entry 0, and the verdicts are the
+    models'."""
+    import ctypes
+    import secp256k1_oracle as o
+    import spends_model as sm
+    import txgen
+    from hkv.sighash import TxBatch
+    from hkv.stdtx import pack_prevouts
+    rng = random.Random(20303)
+    ka, kb, kc, kd = (txgen.Key(rng.randrange(1, o.N)) for _ in range(4))
+    ext = [rng.randbytes(32) + struct.pack("<I", k) for k in range(3)]
+    value = 5 * 10**8
+    # 0: a P2PKH spend, its prevout listed; it pays kb, whom tx 3 spends in the batch
+    # 1: a P2PKH spend with an empty list (its prevout is nowhere in the batch)
+    # 2: a P2WPKH spend (the amount is signed) whose listed prevout is one satoshi off
+    # 3: the child of tx 0, its prevout not listed
+    raws = [_one_input_spend(rng, ext[0], "p2pkh", ka, value, bm._spk("p2pkh", kb)),
+            _one_input_spend(rng, ext[1], "p2pkh", kc, value, bm._spk("p2pkh", kd)),
+            _one_input_spend(rng, ext[2], "p2wpkh", kd, value, bm._spk("p2pkh", ka))]
+    raws.append(_one_input_spend(rng, bm.tx_hash(raws[0]) + struct.pack("<I", 0), "p2pkh", kb, value - 1000,
+                                 bm._spk("p2wpkh", kc)))
+    lacking = (ext[1], bm._spk("p2pkh", kc), value)
+    prevouts = [[(ext[0], bm._spk("p2pkh", ka), value)], [], [(ext[2], bm._spk("p2wpkh", kd), value + 1)], []]
+    ok = model.oracle_input_ok(coracle, None)
+    # (txs 1 and 2 are signed well: the entry tx 1 lacks, and tx 2's at the right value, verify them)
+    assert model.verify_std_tx(raws[1], [lacking], ok)
+    assert model.verify_std_tx(raws[2], [(ext[2], prevouts[2][0][1], value)], ok)
+    want_std = [model.verify_std_tx(r, p, ok) for r, p in zip(raws, prevouts)]
+    want_block = bm.verify_block_txs(raws, prevouts, lambda raw: ok)
+    assert want_std == [True, False, False, False] and want_block == [True, False, False, True]
+
+    n_tx = len(raws)
+    tb = TxBatch(raws)
+    offsets, outpoints, scripts, values = pack_prevouts(tb, prevouts)
+    front = [(rng.randbytes(36), rng.randbytes(25), 7), lacking, (ext[0], rng.randbytes(22), value)]
+    f_scripts = np.array([w for e in front for w in tb.script(e[1])], dtype=np.uint32)
+    st, pool = tb.struct()    # (after every script has gone into the pool)
+    assert offsets.tolist() == [0, 1, 1, 2, 2]
+    shifted = ((offsets + 3).astype(np.uint32),
+               np.concatenate([np.frombuffer(b"".join(e[0] for e in front), dtype=np.uint8), outpoints]),
+               np.concatenate([f_scripts, scripts]),
+               np.concatenate([np.array([e[2] for e in front], dtype=np.uint64), values]))
+    assert shifted[0][0] == 3 and len(shifted[1]) == 5 * 36 and len(shifted[2]) == 10 and len(shifted[3]) == 5
+    cap = int(tb.offsets[-1]) // 41 + 1
+    P = ctypes.POINTER(ctypes.c_uint32)
+
+    def run(prev):
+        head = (ver.ctx, ctypes.byref(st)) + tuple(a.ctypes.data for a in prev)
+        out = {}
+
+        def arrays():
+            return (np.zeros(1, dtype=np.uint32), np.full(n_tx + 1, 0x5A5A5A5A, dtype=np.uint32),
+                    np.full(cap, 0x5A5A5A5A, dtype=np.uint32))
+
+        w, _, _ = arrays()
+        assert ver.lib.hkv_verify_std_txs(*head, -1, w.ctypes.data_as(P)) == 0
+        out["std"] = w.tolist()
+        w, first, src = arrays()
+        assert ver.lib.hkv_verify_block_txs(*head, -1, w.ctypes.data_as(P), first.ctypes.data, src.ctypes.data, cap) == 0
+        out["block"] = (w.tolist(), first.tolist(), src.tolist())
+        w, first, src = arrays()
+        spender = np.full(cap, 0x5A5A5A5A, dtype=np.uint32)
+        sums = np.full(2 * n_tx, 0x5A5A5A5A, dtype=np.uint64)
+        flags = np.full(n_tx, 0x5A, dtype=np.uint8)
+        assert ver.lib.hkv_verify_block_txs_spends(*head, -1, sm.MAX_MONEY, w.ctypes.data_as(P), first.ctypes.data,
+                                                   src.ctypes.data, spender.ctypes.data, cap, sums.ctypes.data,
+                                                   flags.ctypes.data) == 0
+        out["spends"] = (w.tolist(), first.tolist(), src.tolist(), spender.tolist(), sums.tolist(), flags.tolist())
+        return out
+
+    at0, at3 = run((offsets, outpoints, scripts, values)), run(shifted)
+    assert at3 == at0
+    bits = lambda word: [bool(word >> t & 1) for t in range(n_tx)]
+    assert bits(at0["std"][0]) == want_std
+    assert bits(at0["block"][0][0]) == want_block and bits(at0["spends"][0][0]) == want_block
+    assert at0["block"][1] == [0, 1, 2, 3, 4] and at0["block"][2][:4] == [bm.SRC_LIST, bm.SRC_NONE, bm.SRC_LIST, 0]
+    assert at0["spends"][:3] == at0["block"]
+    s = sm.Spends(raws, prevouts, sm.MAX_MONEY)
+    assert at0["spends"][3][:4] == s.spender and at0["spends"][5] == s.flags
+    assert [tuple(at0["spends"][4][2 * t:2 * t + 2]) for t in range(n_tx)] == s.sums

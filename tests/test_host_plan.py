@@ -10,8 +10,16 @@ puts two shards on one device; failed devices are reported once and never
 used again; with no healthy device the call fails without partial output.
 The same program checks the host-batch chunk schedule (chunks sum to the
 shard, start on verdict-word boundaries, stay between one and max_grids + 1
-grids, and equal the stepping they replaced) and the staging layout (parts
-aligned, disjoint and covered by the total)."""
+grids, and equal the stepping they replaced), the staging layout (parts
+aligned, disjoint and covered by the total) and the prevout staging plan of
+the verifyStdTx host forms (plan_prevouts) against a restatement of the
+arithmetic it replaced: 1, 2 and 33 txs with the lists starting at entry 0, 1
+and 7, every input array in a heap block of its exact size; all lists empty
+with null entry arrays (accepted); one step down at the first, a middle and
+the last offset, and null entry arrays with an entry named (refused); the
+sizes for 2^32 - 1 entries with nothing allocated; for accepted calls each
+part at its alignment, no overlap, the total at the last part's end, the
+offsets rebased by the first, and the copies the staging makes."""
 import os
 import subprocess
 
