@@ -42,7 +42,7 @@ HKV_DEV void gej_cmov(gej& r, const gej& a, bool f) {
   fe_cmov(r.z, a.z, f);
 }
 
-// FC (here and in gej_add_tail, gej_add_ge_core, gej_accumulate): the products
+// FC (here and in gej_add_tail, gej_add_ge_core, gej_zaddu, gej_accumulate): the products
 // run the scans' fast forms (hkv_field.h); the throughput launches ask for it.
 // r = 2a for a = 0 (3M + 4S), returned as the same point scaled by 1/2:
 // with A = X^2, B = Y^2, C = B^2, M = X*B, E' = 3A/2,
@@ -112,6 +112,35 @@ HKV_DEV void gej_add_ge_core(gej& r, const gej& a, const fe& az, const fe& bx, c
   rz = fe_is_zero(rr);
   gej_add_tail<FC>(r, a, h, rr);
   if (zr) *zr = h;
+}
+
+// Co-Z addition with update (ZADDU): P = (px, py) and R = (rx, ry) are
+// Jacobian x, y on one common Z that nobody holds. With H = X1 - X2, C = H^2,
+// W1 = X1 C, W2 = X2 C, D = (Y1 - Y2)^2, A1 = Y1 (W1 - W2):
+//   X3 = D - W1 - W2,  Y3 = (Y1 - Y2)(W1 - X3) - A1
+// is P + R on Z H, and (W1, A1) is P on that Z too, so the pair is co-Z again.
+// 4M + 2S; Z H is never formed. Returns (x3, y3), P updated in place to
+// (W1, A1), and the z-ratio h = H.
+// X3, Y3 are the mixed addition's (gej_add_tail with V = W2, H^3 = W1 - W2),
+// limb values aside. A1 is wanted on its own, so Y3 is two products and a
+// subtraction, not a sum scan. Operands are weak-form; (x3, y3) may alias
+// (rx, ry). H == 0 (P = +-R) returns garbage, as gej_add_ge_core does.
+template <bool FC = false>
+HKV_DEV void gej_zaddu(fe& x3, fe& y3, fe& px, fe& py, const fe& rx, const fe& ry, fe& h) {
+  fe c, w2, d, t;
+  fe_sub(h, px, rx);
+  fe_sqr<FC>(c, h);
+  fe_mul<FC>(w2, rx, c);     // W2 = X2 C
+  fe_mul<FC>(px, px, c);     // W1 = X1 C
+  fe_sub(d, py, ry);         // Y1 - Y2
+  fe_sub(t, px, w2);         // H^3
+  fe_mul<FC>(py, py, t);     // A1 = Y1 H^3
+  fe_sqr<FC>(t, d);
+  fe_sub(t, t, px);
+  fe_sub(x3, t, w2);         // X3 = D - W1 - W2
+  fe_sub(t, px, x3);
+  fe_mul<FC>(t, d, t);
+  fe_sub(y3, t, py);         // Y3 = (Y1 - Y2)(W1 - X3) - A1
 }
 
 // Complete "accumulate" step used by every ecmult loop:

@@ -93,7 +93,10 @@ enum {
   HKV_DBG_JOINT_RECODE = 52,
   // a = a scalar k (not 0), b's low limb = j (0..10). The lane runs the joint
   // table build on Q = k G and returns entry j made affine on Q's curve: out =
-  // x | y, normalised.
+  // x | y, normalised. j = 15: out = Zg, normalised. With b's limb 1 non-zero a
+  // is a key's x instead (any field element, on the curve or not) and the
+  // build runs on Q' = (x w, w^2), w = x^3 + 7, as the table launch does;
+  // entries are then affine on that curve, y^2 = x^3 + 7 w^3.
   HKV_DBG_JOINT_TABLE = 53,
   // Group ops (hkv_debug_group_kernel): lane i takes rows 2i and 2i + 1 (n
   // even, n / 2 lanes). a: k1 | z1, b: k2 | w. The lane's points are

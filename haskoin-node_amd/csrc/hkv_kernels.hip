@@ -641,9 +641,18 @@ HKV_DEV void qtable_build(const ge& q, uint32_t* __restrict__ qs, uint32_t n_lan
 
 // The joint form of the table launch (hkv_joint_digits.h, hkv_layout.h JQ_*):
 // the 11 entries (a + b lambda) Q' of the joint digits' orbits, x | y only, in
-// the Booth table's 48 quads per signature. The walk is the Booth one: entry j
-// is entry j - 1 plus a unit image (beta^e x, +-y) of Q', read back from entry
-// 0 at each step, and pass 2 rescales every entry to the last one's Z. The
+// the Booth table's 48 quads per signature. Entry j is entry j - 1 plus a unit
+// image (beta^e x, +-y) of Q'. Q' and 2Q start on one Z, so the walk is nine
+// co-Z additions with update (hkv_group.h gej_zaddu): Qc = (Xq, Yq), Q' on the
+// running point's Z, stays in registers, each step leaves both on the new Z,
+// and no Z is carried. A step with e != 0 (three of the nine) turns Xq into
+// the image's x in place and takes it back from the updated image, Xq =
+// beta^-e W1, with beta^-1 = beta^2: a beta product before and after. (The
+// other way, Xq H^2 beside the image, holds Xq and H^2 across the addition
+// and spilled at 128 VGPRs, where this one takes 120 and no scratch.) Pass 2
+// rescales entries 9..1 to the last one's Z, where Qc already stands: it is
+// entry 0. The running product of pass 2 ends as rho = H_2 ... H_10, and
+// Zg = Z2 rho. In product scans: 7 + 4, 9 x 6 + 3 x 2 the walk, 45 pass 2. The
 // nine z-ratios H_2..H_10 wait between the passes where nothing else lives:
 // four in LDS (idle in this launch: 32 KiB per workgroup, four workgroups per
 // CU), two in the lane's 4 spare quads, one in its Zg slot (written after the
@@ -689,79 +698,84 @@ struct JqPark {
     }
   }
 };
+// a := beta^e a, e = 1, 2
+template <bool FC>
+HKV_DEV void fe_mul_beta_pow(fe& a, uint32_t e) {
+  fe beta, b;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
+  fe_mul<FC>(b, a, beta);
+  if (e == 2u) {  // beta^2 x = -(x + beta x)
+    fe_add(b, a, b);
+    fe_neg(b, b);
+  }
+  a = b;
+}
 // zslot: the lane's Zg slot (the caller writes Zg there after the build)
+// FC: the products' fast scans (hkv_field.h). -DHKV_QTABLE_FC=0 / 1 is the A/B.
+#ifndef HKV_QTABLE_FC
+#define HKV_QTABLE_FC 0
+#endif
+template <bool FC = (HKV_QTABLE_FC != 0)>
 HKV_DEV void qtable_build_joint(const ge& q, uint32_t* __restrict__ qs, uint32_t n_lanes, uint32_t lane, uint4* zslot,
                                 JqLds* lds, fe& Zg) {
   static_assert(JD_ENTRIES == JQ_ENTRIES, "one entry per orbit");
   const JqPark park = {lds, reinterpret_cast<uint4*>(qs) + (size_t)JQ_ENTRIES * JQ_QUADS_PER_ENTRY * n_lanes +
                                 (size_t)lane * JQ_SPARE_QUADS,
                        zslot, jq_ptr(qs, n_lanes, lane, JQ_ENTRIES - 1, 0)};
-  gej p2, pj;
+  gej p2;
   gej_set_ge(p2, q);
-  gej_double(p2, p2);  // 2Q (Jacobian, scale Z2)
+  gej_double<FC>(p2, p2);  // 2Q (Jacobian, scale Z2)
+  fe xq, yq;               // Qc: Q' on the running point's Z
   {
-    fe z2, qx, qy;  // Q' = phi_Z2(Q) = (x Z2^2, y Z2^3)
-    fe_sqr(z2, p2.z);
-    fe_mul(qx, q.x, z2);
-    fe_mul(z2, z2, p2.z);
-    fe_mul(qy, q.y, z2);
-    quads_store(jq_ptr(qs, n_lanes, lane, 0, 0), qx);
-    quads_store(jq_ptr(qs, n_lanes, lane, 0, 2), qy);
+    fe z2;  // Q' = phi_Z2(Q) = (x Z2^2, y Z2^3)
+    fe_sqr<FC>(z2, p2.z);
+    fe_mul<FC>(xq, q.x, z2);
+    fe_mul<FC>(z2, z2, p2.z);
+    fe_mul<FC>(yq, q.y, z2);
   }
   quads_store(jq_ptr(qs, n_lanes, lane, 1, 0), p2.x);
   quads_store(jq_ptr(qs, n_lanes, lane, 1, 2), p2.y);
-  pj.x = p2.x;
-  pj.y = p2.y;
-  fe_set_u32(pj.z, 1);
 #pragma unroll 1
   for (int j = 2; j < JQ_ENTRIES; ++j) {
-    // entry j = entry j - 1 + (-1)^s lambda^e Q' (uniform in j)
+    // entry j = entry j - 1 + (-1)^s lambda^e Q' (uniform in j); p2.x, p2.y: the running point
     const uint32_t e = (JD_STEP_E >> (2 * (j - 1))) & 3u;
     const bool neg = ((JD_STEP_S >> (j - 1)) & 1u) != 0;
-    bool hz, rz;
-    fe h, tx, ty;
-    jq_load(qs, n_lanes, lane, 0, 0, tx);
-    if (e != 0u) {
-      fe beta, bx;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) beta.v[k] = FE_BETA[k];
-      fe_mul(bx, tx, beta);
-      if (e == 2u) {  // beta^2 x = -(x + beta x)
-        fe_add(bx, tx, bx);
-        fe_neg(bx, bx);
-      }
-      tx = bx;
-    }
-    jq_load(qs, n_lanes, lane, 0, 2, ty);
-    fe_cneg(ty, ty, neg);
-    gej_add_ge_core(pj, pj, pj.z, tx, ty, hz, rz, &h);
-    if (j < JQ_ENTRIES - 1) {  // (the last entry's x, y wait in pj)
-      quads_store(jq_ptr(qs, n_lanes, lane, j, 0), pj.x);
-      quads_store(jq_ptr(qs, n_lanes, lane, j, 2), pj.y);
+    fe h;
+    if (e != 0u) fe_mul_beta_pow<FC>(xq, e);  // the image's x
+    fe_cneg(yq, yq, neg);
+    gej_zaddu<FC>(p2.x, p2.y, xq, yq, p2.x, p2.y, h);
+    fe_cneg(yq, yq, neg);                    // Yq = +-A1
+    if (e != 0u) fe_mul_beta_pow<FC>(xq, 3u - e);  // Xq = beta^-e W1
+    if (j < JQ_ENTRIES - 1) {  // (the last entry's x, y wait in p2)
+      quads_store(jq_ptr(qs, n_lanes, lane, j, 0), p2.x);
+      quads_store(jq_ptr(qs, n_lanes, lane, j, 2), p2.y);
     }
     park.store(j - 2, h);
   }
-  fe_mul(Zg, p2.z, pj.z);  // total scale: phi_Z2 then phi_Zc, Zc = pj.z
-  fe rho;
-  fe_set_u32(rho, 1);
+  // Qc stands at the last Z: entry 0 at the final scale
+  quads_store(jq_ptr(qs, n_lanes, lane, 0, 0), xq);
+  quads_store(jq_ptr(qs, n_lanes, lane, 0, 2), yq);
+  fe rho;  // rho_j = prod_{k > j} H_k
+  park.load(JQ_ENTRIES - 3, rho);
 #pragma unroll 1
-  for (int j = JQ_ENTRIES - 2; j >= 0; --j) {
+  for (int j = JQ_ENTRIES - 2;; --j) {
     fe x, y, t;
-    if (j >= 1) {
-      park.load(j - 1, t);  // H_{j+1}
-      fe_mul(rho, rho, t);
-    }
     jq_load(qs, n_lanes, lane, j, 0, x);
     jq_load(qs, n_lanes, lane, j, 2, y);
-    fe_sqr(t, rho);
-    fe_mul(x, x, t);
-    fe_mul(t, t, rho);
-    fe_mul(y, y, t);
+    fe_sqr<FC>(t, rho);
+    fe_mul<FC>(x, x, t);
+    fe_mul<FC>(t, t, rho);
+    fe_mul<FC>(y, y, t);
     quads_store(jq_ptr(qs, n_lanes, lane, j, 0), x);
     quads_store(jq_ptr(qs, n_lanes, lane, j, 2), y);
+    if (j == 1) break;
+    park.load(j - 2, t);  // H_j
+    fe_mul<FC>(rho, rho, t);
   }
-  quads_store(park.last, pj.x);
-  quads_store(park.last + 2, pj.y);
+  fe_mul<FC>(Zg, p2.z, rho);  // total scale: phi_Z2 then phi_Zc, Zc = H_2 ... H_10
+  quads_store(park.last, p2.x);
+  quads_store(park.last + 2, p2.y);
 }
 
 // The shared doubling chain of k1 * Q' + k2 * lambda(Q'), 33 radix-16 windows
@@ -997,8 +1011,9 @@ __global__ void __launch_bounds__(WG, 2) hkv_ecmult_kernel(uint32_t* __restrict_
 //     signatures (i0 .. i0 + cn, cn a multiple of WG). Signature s of the
 //     chunk owns table slot s of qs and the Zg slot behind the chunk's tables
 //     (hkv_layout.h HKV_REC_CHUNK). The chain launch is bound by VALU issue,
-//     and the table launch, which streams 2.4 KB per signature, issues VALU
-//     at about 85 % of the chain's rate too. A 1M
+//     and the table launch, which moves 1.9 KB per signature in its joint
+//     form (within a quarter of its memory time: DESIGN 4.2, round 16), still
+//     issues VALU at about 85 % of the chain's rate. A 1M
 //     chunk is four times the resident grid, so a workgroup slot that frees
 //     early takes the next workgroup. The earlier form, one kernel whose
 //     resident lanes each looped over four signatures, ran the same
@@ -3009,9 +3024,24 @@ __global__ void __launch_bounds__(WG) hkv_debug_kernel(uint32_t op, uint32_t n, 
       sc zero;
       for (int k = 0; k < 8; ++k) zero.v[k] = 0;
       ge_set_g(g);
-      if (!ecmult_simple(q, u, zero, g)) q = g;
+      if (y.v[1] != 0u) {  // a is the key's x: Q' as the table launch forms it (lane_q)
+        fe w;
+        fe_sqr(w, x);
+        fe_mul(w, w, x);
+        fe_set_u32(z, 7);
+        fe_add(w, w, z);
+        fe_mul(q.x, x, w);
+        fe_sqr(q.y, w);
+      } else if (!ecmult_simple(q, u, zero, g)) {
+        q = g;
+      }
       fe Zg, zi, zi2, t;
       qtable_build_joint(q, tab, 1u, 0u, reinterpret_cast<uint4*>(tab) + QTAB_QUADS, &park, Zg);
+      if ((y.v[0] & 15u) == 15u) {
+        fe_normalize(Zg);
+        for (int k = 0; k < 8; ++k) res[k] = Zg.v[k];
+        break;
+      }
       const int j = (int)(y.v[0] & 15u) < JD_ENTRIES ? (int)(y.v[0] & 15u) : 0;
       jq_load(tab, 1u, 0u, j, 0, x);
       jq_load(tab, 1u, 0u, j, 2, z);
